@@ -36,6 +36,15 @@ timing barrier and the max over ranks).  --dry-run stops before the GPU (gloo) a
 rank layout.  --dist-backend gloo --same-device runs the multi-rank body with every rank on
 device 0 (a 1-GPU box rehearsing the N-GPU data path; --dump-state DIR writes each rank's end
 state and carried key for the parity test).  Rank 0 prints ONE JSON line.
+
+A plain run does only what `value` needs: set-up, warm-up, one untimed-for-the-line pass through
+the timing path, clock settle, the K timed steps, the line.  --full adds the figures beside it:
+`unsettled` (that first pass: the same K steps right after the warm-up), `episode_value` (a
+window that crosses every env's episode end) and `cpu_baseline` (the C restatement on this host's
+cores with its end-state parity check against the GPU); without --full these keys are null.
+--dump-outputs DIR writes what the timed run's last call returned to its caller (obs, rewards and
+dones per agent type, the env state, the carried key) as DIR/<name>.npy right after the timed
+run; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -54,6 +63,7 @@ CONFIG = "2_player_fq_fqc"
 PEAK_HBM_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 N_CU, CLOCK_HZ = 256, 2.4e9    # MI355X CUs, max engine clock (MI355X_MICROARCH.md)
 CPU_STEPS = 64                 # CPU baseline / parity: one full episode (incl. the auto-reset)
+DUMP_BYTES, DUMP_SEED = 64_000_000, 0  # --dump-outputs: size limit of all files together, seed of the env-row sample
 PROFILE = "r*_kernel_profile.json"  # profiles/: rocprof figures of the metric kernel (tools/profile_round.sh), newest round
 
 
@@ -68,7 +78,11 @@ def parse_args(argv=None):
     ap.add_argument("--envs", type=int, default=NUM_ENVS, help="envs per GPU")
     ap.add_argument("--n-msgs", type=int, default=400_000, help="synthetic day length (messages)")
     ap.add_argument("--mid", type=int, default=2_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the same steps timed before the "
+                         "clock settle (unsettled), the episode window (episode_value, --episode-steps) and the "
+                         "CPU baseline with its parity check (cpu_baseline, --no-cpu-baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--config", default=CONFIG, help="builtin env config (the metric: 2_player_fq_fqc)")
     ap.add_argument("--agents", default=None, help="number_of_agents_per_type override, e.g. 5,5 (Speed_test sweep)")
     ap.add_argument("--n-data-msg", type=int, default=None, help="n_data_msg_per_step override (Speed_test: 100, 1)")
@@ -88,8 +102,12 @@ def parse_args(argv=None):
     ap.add_argument("--same-device", action="store_true",
                     help="every rank on device 0 (with --dist-backend gloo: the N-rank body on a 1-GPU box)")
     ap.add_argument("--episode-steps", type=int, default=66,
-                    help="also time one launch of this many steps from state0 that crosses every env's episode "
-                         "end and auto-reset (reported as episode_value, not value; 0 = off)")
+                    help="with --full: also time one launch of this many steps from state0 that crosses every "
+                         "env's episode end and auto-reset (reported as episode_value, not value; 0 = off)")
+    ap.add_argument("--dump-outputs", default=None,
+                    help="directory: after the timed run, write what its last step returned to the caller (obs, "
+                         "rewards, dones per agent type, the env state, the carried key) as <name>.npy, float32 / "
+                         "float64, at most 64 MB (a fixed seeded sample of env rows beyond that)")
     ap.add_argument("--dump-state", default=None,
                     help="directory: each rank writes rank<r>.npz (end state, carried key) after the timed run")
     return ap.parse_args(argv)
@@ -211,13 +229,51 @@ def timed_window(K: int, max_steps: int, ctr0: int = 0) -> str:
     return f"timed steps 0-{K - 1} from the reset state (step counter {ctr0}), {max_steps}-step episodes: {what}"
 
 
-def compare_states(env, cpu, gpu) -> str:
-    """Integer words of the record bit-exact, float words within 1e-5 (SURVEY.md 8(d))."""
-    import numpy as np
-    L = env.layout
+def float_words(L):
+    """The words of an env's state record that hold float32 values (the others are int32)."""
     fw = [L.off_world + 3, L.off_world + 4]
     for k, off in zip(L.agent_kinds, L.agent_offsets):
         fw += [off + 3, off + 4] if k == 0 else [off + j for j in (0, 4, 5, 6, 7, 8, 9, 10, 11, 12)]
+    return fw
+
+
+def dump_outputs(path, env, ret, key, rank, world):
+    """--dump-outputs: what the timed path's last call returned (obs, state, rewards, dones) and the
+    carried key, one <name>.npy each (rank r > 0: <name>.rank<r>.npy): float32 values as they are,
+    bools as float32 0 / 1, int32 words as float64.  The state record goes out as its int words
+    (state_int) and its float words (state_float).  All ranks together stay under DUMP_BYTES: beyond
+    it every per-env array keeps the same seeded sample of env rows, listed in env_rows."""
+    import numpy as np
+    import torch
+    obs, state, rewards, dones, _ = ret
+    L, buf = env.layout, state.buf
+    E = buf.shape[0]
+    fw = float_words(L)
+    iw = sorted(set(range(buf.shape[1])) - set(fw))
+    dev = buf.device
+    per_env = {"state_int": (buf[:, torch.tensor(iw, device=dev)], np.float64),
+               "state_float": (buf[:, torch.tensor(fw, device=dev)].contiguous().view(torch.float32), np.float32),
+               "done_all": (dones["__all__"], np.float32)}
+    for t in range(len(obs)):
+        per_env[f"obs_type{t}"] = (obs[t], np.float32)
+        per_env[f"rewards_type{t}"] = (rewards[t], np.float32)
+        per_env[f"dones_type{t}"] = (dones["agents"][t], np.float32)
+    row_bytes = 8 + sum(x[0].numel() * np.dtype(dt).itemsize for x, dt in per_env.values())
+    n = min(E, (DUMP_BYTES // world - 4096) // row_bytes)
+    rows = np.arange(E) if n == E else np.sort(np.random.default_rng(DUMP_SEED).choice(E, n, replace=False))
+    sel = torch.from_numpy(rows).to(dev)
+    os.makedirs(path, exist_ok=True)
+    ext = ".npy" if rank == 0 else f".rank{rank}.npy"
+    np.save(os.path.join(path, "env_rows" + ext), rows.astype(np.float64))
+    np.save(os.path.join(path, "carried_key" + ext), key.cpu().numpy().view(np.uint32).astype(np.float64))
+    for name, (x, dt) in per_env.items():
+        np.save(os.path.join(path, name + ext), x[sel].cpu().numpy().astype(dt))
+
+
+def compare_states(env, cpu, gpu) -> str:
+    """Integer words of the record bit-exact, float words within 1e-5 (SURVEY.md 8(d))."""
+    import numpy as np
+    fw = float_words(env.layout)
     mask = np.ones(cpu.shape[1], bool)
     mask[fw] = False
     bad = int(((cpu != gpu) & mask[None, :]).sum())
@@ -360,18 +416,19 @@ def main(argv=None):
     T = (args.steps_per_call if args.steps_per_call > 0 else max(args.steps, 1)) if args.mode == "rollout" else 1
     kbuf = [master0.clone(), torch.empty(2, dtype=torch.int32, device=dev)]
     nstep = [0]
+    last = [None]  # what the latest call returned to its caller (--dump-outputs)
 
     def run(n_steps, per_call=None):  # n_steps env steps continuing the rollout from (state, kbuf)
         while n_steps > 0:
             n, k = min(per_call or T, n_steps), nstep[0]
             if args.mode == "rollout":
-                env.rollout_sampled(kbuf[k % 2], kbuf[(k + 1) % 2], state, params, n, n_slices=args.slices,
-                                    key_e0=key_e0, key_n=key_n)
+                last[0] = env.rollout_sampled(kbuf[k % 2], kbuf[(k + 1) % 2], state, params, n,
+                                              n_slices=args.slices, key_e0=key_e0, key_n=key_n)
             else:  # Speed_test's three calls, each its own launch: split, Discrete.sample, env.step
                 ks = split_keys(kbuf[k % 2].reshape(1, 2), key_n + 1)[0]
                 kbuf[(k + 1) % 2].copy_(ks[0])
                 sk = ks[1 + key_e0:1 + key_e0 + E].contiguous()
-                env.step(sk, state, env.sample_actions(sk), params)
+                last[0] = env.step(sk, state, env.sample_actions(sk), params)
             nstep[0] = k + 1
             n_steps -= n
 
@@ -401,7 +458,10 @@ def main(argv=None):
 
     run(args.warmup)                          # Speed_test's compile run
     # the same K steps timed right after the warm-up, as Speed_test times them (reported beside
-    # `value` as `unsettled`: the GPU has not reached its loaded clock yet)
+    # `value` as `unsettled` with --full: the GPU has not reached its loaded clock yet).  A plain run
+    # keeps this pass (K steps, about a millisecond) and drops its figure: the first pass through
+    # timed() pays the host's one-time costs of the timing path (first event record, first barrier),
+    # which read as 2-4 % of a 20-step `value` when the timed run itself was that first pass
     uns_elapsed, uns_kern_ms = timed() if args.settle_ms > 0 else (None, None)
     # clock settle (untimed): calls of the timed run's length (T steps, so every launch a profiler
     # sees is the timed shape) until --settle-ms of wall time has passed, then back to state0 /
@@ -418,8 +478,10 @@ def main(argv=None):
         os.makedirs(args.dump_state, exist_ok=True)
         np.savez(os.path.join(args.dump_state, f"rank{rank}.npz"), state=state.buf.cpu().numpy(),
                  key=kbuf[nstep[0] % 2].cpu().numpy(), key_e0=key_e0, key_n=key_n, steps=args.steps)
+    if args.dump_outputs:  # what the timed run's last call returned (the output buffers are reused by later calls)
+        dump_outputs(args.dump_outputs, env, last[0], kbuf[nstep[0] % 2], rank, world)
     episode = None
-    if args.episode_steps > 0:
+    if args.full and args.episode_steps > 0:
         # the same rollout over a window that holds every env's episode end: the episode-end unwind /
         # doom trades and the auto-reset (marl_env.py:787-803) inside the timed region, one call of
         # episode_steps steps (rollout mode), after the timed run at the settled clock
@@ -433,7 +495,7 @@ def main(argv=None):
                             "are inside the window")}
 
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         thr = args.cpu_threads or cpu_share()[0]
         cpu, cpu_state = cpu_baseline(env, day, state0, master0, thr)
         restart()                             # the same rollout on the GPU, for the parity check
@@ -520,7 +582,7 @@ def main(argv=None):
                        "kernel_ms": round(uns_kern_ms, 5),
                        "what": (f"the same {args.steps} steps from state0 timed right after the {args.warmup} "
                                 "warm-up steps, before the clock settle (Speed_test's order; --settle-ms 0 "
-                                "makes this the value)")} if uns_elapsed is not None else None),
+                                "makes this the value)")} if args.full and uns_elapsed is not None else None),
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "episode_value": episode,
         "higher_is_better": True,

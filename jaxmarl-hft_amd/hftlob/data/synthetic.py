@@ -41,7 +41,7 @@ class LobsterDay:
 def generate_day(n_msgs: int = 400_000, seed: int = 20260403, mid: int = 2_000_000, tick: int = 100,
                  snap_every: int = 6400, levels: int = 10, day_start: int = 34200, day_end: int = 57600) -> LobsterDay:
     rng = np.random.Generator(np.random.PCG64(seed))
-    asks, bids = SortedDict(), SortedDict()       # price -> list of [oid, qty]
+    asks, bids = SortedDict(), SortedDict()       # price -> {oid: qty} in arrival order (the level's queue)
     where = {}                                    # oid -> (side, price)
     next_oid = 10_000_000
 
@@ -50,7 +50,7 @@ def generate_day(n_msgs: int = 400_000, seed: int = 20260403, mid: int = 2_000_0
         oid = next_oid
         next_oid += 1
         book = bids if side == 1 else asks
-        book.setdefault(price, []).append([oid, qty])
+        book.setdefault(price, {})[oid] = qty
         where[oid] = (side, price)
         return oid
 
@@ -58,14 +58,12 @@ def generate_day(n_msgs: int = 400_000, seed: int = 20260403, mid: int = 2_000_0
         side, price = where[oid]
         book = bids if side == 1 else asks
         lvl = book[price]
-        for k, (o, q) in enumerate(lvl):
-            if o == oid:
-                if q - qty <= 0:
-                    lvl.pop(k)
-                    del where[oid]
-                else:
-                    lvl[k][1] = q - qty
-                break
+        q = lvl[oid]
+        if q - qty <= 0:
+            del lvl[oid]
+            del where[oid]
+        else:
+            lvl[oid] = q - qty
         if not lvl:
             del book[price]
 
@@ -95,12 +93,12 @@ def generate_day(n_msgs: int = 400_000, seed: int = 20260403, mid: int = 2_000_0
         for k in range(levels):
             if k < len(a_lv):
                 books[row, 4 * k] = a_lv[k][0]
-                books[row, 4 * k + 1] = sum(q for _, q in a_lv[k][1])
+                books[row, 4 * k + 1] = sum(a_lv[k][1].values())
             else:
                 books[row, 4 * k] = EMPTY_ASK
             if k < len(b_lv):
                 books[row, 4 * k + 2] = b_lv[k][0]
-                books[row, 4 * k + 3] = sum(q for _, q in b_lv[k][1])
+                books[row, 4 * k + 3] = sum(b_lv[k][1].values())
             else:
                 books[row, 4 * k + 2] = EMPTY_BID
 
@@ -126,7 +124,7 @@ def generate_day(n_msgs: int = 400_000, seed: int = 20260403, mid: int = 2_000_0
             rest, opp = qty, (asks if side == 1 else bids)
             while rest > 0 and len(opp) and (opp.keys()[0] <= price if side == 1 else opp.keys()[-1] >= price):
                 lvl_p = opp.keys()[0] if side == 1 else opp.keys()[-1]
-                o, q = opp[lvl_p][0]
+                o, q = next(iter(opp[lvl_p].items()))
                 take = min(q, rest)
                 remove_qty(o, take)
                 rest -= take
@@ -137,7 +135,7 @@ def generate_day(n_msgs: int = 400_000, seed: int = 20260403, mid: int = 2_000_0
         elif r < 0.60 or r < 0.90:
             oid = picker.pick(pick[i])
             side, price = where[oid]
-            q = _qty_of(asks if side == -1 else bids, price, oid)
+            q = (asks if side == -1 else bids)[price][oid]
             if r < 0.60 and q > 1:
                 c = int(rng.integers(1, q))
                 msgs[i] = (2, side, c, price, oid, oid, ts, tn)
@@ -149,7 +147,7 @@ def generate_day(n_msgs: int = 400_000, seed: int = 20260403, mid: int = 2_000_0
             side = int(side_draw[i])
             book = bids if side == 1 else asks
             lvl_p = book.keys()[-1] if side == 1 else book.keys()[0]
-            oid, q = book[lvl_p][0]
+            oid, q = next(iter(book[lvl_p].items()))
             e = int(rng.integers(1, q + 1))
             msgs[i] = (4, side, e, lvl_p, oid, oid, ts, tn)
             remove_qty(oid, e)
@@ -173,10 +171,3 @@ class _LivePicker:
             u = self.rng.random()
         self.keys, self.stale = list(self.where.keys()), 0
         return self.keys[int(u * len(self.keys)) % len(self.keys)]
-
-
-def _qty_of(book, price, oid):
-    for o, q in book[price]:
-        if o == oid:
-            return q
-    raise KeyError(oid)

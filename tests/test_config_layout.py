@@ -90,11 +90,11 @@ def test_cancel_mode_values():
         pack_env_cfg(cfg, 4, 10_000, True)
 
 
-REF_CFG_DIR = "/root/reference/config/env_configs"
+# the reference's config/env_configs/*.json, file for file
+REF_CFG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_env_configs")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG_DIR), reason="reference configs not mounted")
-@pytest.mark.parametrize("fname", sorted(os.listdir(REF_CFG_DIR)) if os.path.isdir(REF_CFG_DIR) else [])
+@pytest.mark.parametrize("fname", sorted(os.listdir(REF_CFG_DIR)))
 def test_reference_env_configs_pack(fname):
     """Every env config the reference ships loads with our loader and packs for the HIP path."""
     from hftlob.config_io import load_config_from_file
@@ -104,7 +104,6 @@ def test_reference_env_configs_pack(fname):
     assert c.action_words == sum(c.types[t].n_agents * c.types[t].action_width for t in range(c.n_types))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG_DIR), reason="reference configs not mounted")
 def test_reference_env_config_fixture_is_current():
     """tests/golden/reference_env_configs.json (what the GPU run test steps) is the reference's
     config/env_configs as our loader reads them."""

@@ -4,7 +4,7 @@ The kernels replace ``jnp.floor_divide(a, tick_size)`` on int32 by a multiply wi
 magic number (``tick_floordiv``) and ``jnp.floor_divide(x, float(tick_size))`` on float32 by a
 reciprocal plus one exact correction (``tick_ffloordiv``), with the jnp formula as the fallback
 outside its bounds.  ``World_EnvironmentConfig.tick_size`` is a free field
-(/root/reference/gymnax_exchange/jaxob/jaxob_config.py:213), used by the market maker's quotes
+(the reference's gymnax_exchange/jaxob/jaxob_config.py:213), used by the market maker's quotes
 (mm_env.py:990-991,1049-1051), the execution agent's prices (exec_env.py:838-932) and the rewards'
 reference prices.  Each case generates a synthetic day on that tick's price grid and compares the
 HIP env step by step with the oracle, whose floor divisions are the jnp formulas

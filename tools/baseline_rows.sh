@@ -10,7 +10,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out/rows_$T
 mkdir -p $O
 cd $GRAFT_REPO_ROOT
 B="timeout -k 10 300 python bench.py"
-$B --config mm_debug_fixed_quant --envs 1 > $O/c1_1env.json 2> $O/err.log || exit 1
+$B --full --config mm_debug_fixed_quant --envs 1 > $O/c1_1env.json 2> $O/err.log || exit 1
 $B --no-cpu-baseline --mid 28000000 > $O/c3_mid28m.json 2>> $O/err.log || exit 2
 $B --no-cpu-baseline --steps 640 > $O/c3_640steps.json 2>> $O/err.log || exit 3
 $B --no-cpu-baseline --mode step > $O/c3_stepmode.json 2>> $O/err.log || exit 4

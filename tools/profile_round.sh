@@ -21,7 +21,7 @@ fi
 echo "{\"kernel\": \"$KER\", \"slices\": $G, \"steps_per_launch\": $SPL, \"stats_steps_per_launch\": $SSPL, \"commit\": \"${PROF_COMMIT:-}\"}" > $O/shape.json
 [ -n "$SKIP_TESTS" ] || timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread -p no:cacheprovider > $O/pytest.log 2>&1 || exit 8
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit 9
-timeout -k 10 600 python bench.py --slices $G > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 600 python bench.py --full --slices $G > $O/bench.json 2> $O/bench.err || exit 1
 cd /tmp && export TMPDIR=/tmp
 # (--episode-steps 0: every k_env_rollout launch of a profiled run then has the run's length, so the
 #  per-launch averages divide by one steps-per-launch figure; the episode window's extra 66-step launch
@@ -41,7 +41,7 @@ timeout -k 10 400 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_LDS_BANK_CONFLICT S
 cd $GRAFT_REPO_ROOT
 timeout -k 10 300 python bench.py --mode step --no-cpu-baseline > $O/bench_stepmode.json 2> $O/bench_stepmode.err || exit 7
 # the driver's command itself (20 steps, CPU baseline included) and the other configs' bench lines
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err || exit 10
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err || exit 10
 timeout -k 10 300 python bench.py --envs 512 --no-cpu-baseline > $O/bench_c2_512.json 2> $O/bench_c2.err || exit 11
 timeout -k 10 300 python bench.py --config 3_player_fq_fqc_dir --envs 1024 --no-cpu-baseline > $O/bench_c5_1024.json 2> $O/bench_c5.err || exit 12
 # phase stamps of the rollout kernel at the driver's launch length (needs ab/stamps.so: make -C jaxmarl-hft_amd/csrc stamps)
