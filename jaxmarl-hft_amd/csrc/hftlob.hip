@@ -713,6 +713,10 @@ constexpr int PAD_FILT = 128, PAD_SCR = PAD_FILT + FILT_WORDS, PAD_WORDS = PAD_S
 // lanes of column loads read)
 constexpr int PAD_CARRY = 96;
 static_assert(FILT_WORDS >= 64 && FILT_WORDS % 64 == 0 && PAD_WORDS - PAD_SCR == 64, "filter words per lane, 64-word scratch row");
+static_assert(PAD_CARRY + 13 <= PAD_FILT, "the rollout's 13 carry words end before the filter words");
+// the LDS words of one env's book (book_bind's carve-up): what hftlob_book_process reserves and
+// what lds_map gives the book inside an env's workgroup
+__host__ __device__ constexpr int book_words(int nO, int nT) { return 12 * nO + 8 * nT + PAD_WORDS; }
 template <int S>
 struct Book {
     Side<S> a, b;
@@ -2830,7 +2834,7 @@ __host__ __device__ inline bool kb_ok(const hftlob_env_cfg& c) {  // (a step's r
 }
 __host__ __device__ inline int kb_words(const hftlob_env_cfg& c) { return 6 + c.n_agents + c.n_action_msgs; }
 // LDS carve-up of one env's workgroup (words): [agent rows (C+A)*8][action extras][book: asks 6nO,
-// bids 6nO, trades 8nT, pad 256][key batches].  The agent rows can live IN the trade log instead:
+// bids 6nO, trades 8nT, pad PAD_WORDS][key batches].  The agent rows can live IN the trade log instead:
 // it is free from the step's start until trades_fill, which then runs once the rows are read.
 // (Speed_test's [5,5] agents: 60 rows, 1.9 KB less per env, 16 envs per CU instead of 14.)
 // The rows may span two message chunks (C + A <= 128): the second chunk's agent rows are read into
@@ -2855,7 +2859,7 @@ __host__ __device__ inline LdsMap lds_map(const hftlob_env_cfg& c, int nO, int n
     m.axs = rw;
     m.book = rw + ((c.n_agents * 6 + 3) & ~3);
     m.rows = alias ? m.book + 12 * nO : 0;  // (the trade log)
-    m.kb = m.book + 12 * nO + 8 * nT + PAD_WORDS;
+    m.kb = m.book + book_words(nO, nT);
     m.words = m.kb + (kb_ok(c) ? KB_STEPS * kb_words(c) : 0);
     return m;
 }
@@ -3871,7 +3875,7 @@ int hftlob_book_process(const hftlob_lob_cfg* cfg, int n_env, int n_msg, const u
     const int S = slot_sets(cfg->n_orders > cfg->n_trades ? cfg->n_orders : cfg->n_trades);
     hipStream_t st = (hipStream_t)stream;
     dim3 g(n_env), b(ENV_BLOCK);
-    const size_t shm = 4 * ((size_t)12 * cfg->n_orders + 8 * cfg->n_trades + 64 * 4);
+    const size_t shm = 4 * (size_t)book_words(cfg->n_orders, cfg->n_trades);
 #define LAUNCH_BOOK(SS, RC) hipLaunchKernelGGL((k_book_process<SS, RC>), g, b, shm, st, *cfg, n_env, n_msg, keys, msgs, \
                                                asks, bids, trades, best_asks, best_bids)
     if (rc_) {

@@ -112,11 +112,11 @@ def neg1_trade_streams(n_env, n_msg, seed, price0=1000):
     return out
 
 
-def full_book_messages(n_env, seed, nO=100, lo=0.85, hi=1.0, price0=1000):
+def full_book_messages(n_env, seed, nO=100, lo=0.85, hi=1.0, price0=1000, init_id=-2):
     """Init messages that leave each side holding between lo * nO and hi * nO orders (per env and
     side), at distinct prices behind the touch, a third of them with the init id (-2, the
     get_init_id_match candidates): books whose last slot is occupied or not, and a few free rows,
-    for the no-op skip's room test."""
+    for the no-op skip's room test.  (nO = 1: a side holds one order or none.)"""
     rng = np.random.Generator(np.random.PCG64(seed))
     rows = []
     for e in range(n_env):
@@ -125,13 +125,14 @@ def full_book_messages(n_env, seed, nO=100, lo=0.85, hi=1.0, price0=1000):
             n = int(rng.integers(int(lo * nO), int(hi * nO) + 1))
             for k in range(n):
                 price = price0 - side * (3 + k) + (0 if side == 1 else 0)
-                oid = -2 if rng.random() < 0.33 else 100000 + 1000 * (side + 1) + k
+                oid = init_id if rng.random() < 0.33 else 100000 + 1000 * (side + 1) + k
                 r.append((1, side, int(rng.integers(1, 50)), price, oid, -2 - k, 34199, k))
         rows.append(r)
     m = max(len(r) for r in rows)
     out = np.zeros((n_env, m, 8), dtype=np.int32)  # doNothing padding
     for e, r in enumerate(rows):
-        out[e, :len(r)] = r
+        if r:
+            out[e, :len(r)] = r
     return out
 
 
@@ -316,4 +317,78 @@ def miss_empty_streams(n_env, seed, price0=1000, n_chunks=4, nO=100):
                 tn += int(rng.integers(1, 500))
                 out[e, k] = (typ, sd, q, price, oid, int(rng.integers(1, 6)), t, tn)
                 k += 1
+    return out
+
+
+def prefilled_trades(n_env, nT, seed, rows=None, price0=1000):
+    """Incoming trade logs whose first `rows` rows (default nT - 2, at least 0) hold earlier trades
+    (col 4, the trade's TIME, is not -1) and whose other rows are free (-1): the next trades go to
+    rows nT - 2 and nT - 1, and every later one overwrites the last row (match_order's -1 index)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n = max(0, nT - 2) if rows is None else rows
+    t = np.full((n_env, nT, 8), -1, np.int32)
+    t[:, :n, 0] = price0 + rng.integers(-3, 4, (n_env, n))
+    t[:, :n, 1] = rng.integers(1, 40, (n_env, n)) * rng.choice([-1, 1], (n_env, n))
+    t[:, :n, 2] = rng.integers(1000, 5000, (n_env, n))
+    t[:, :n, 3] = rng.integers(1000, 5000, (n_env, n))
+    t[:, :n, 4] = 34100 + np.arange(n)[None, :]
+    t[:, :n, 5] = rng.integers(0, 10**9, (n_env, n))
+    t[:, :n, 6] = rng.integers(1, 6, (n_env, n))
+    t[:, :n, 7] = rng.integers(1, 6, (n_env, n))
+    return t
+
+
+def init_range_streams(n_env, n_msg, seed, init_id=-2, price0=1000, nO=100):
+    """noop_streams with a sixth of the messages replaced by the two halves of get_init_id_match's
+    id range test [init_id - 2 * book_depth, init_id]: non-crossing adds carrying an id in
+    [init_id - 20, init_id - 7] (init-id rows at book_depth 10, ordinary rows at book_depth 3 and 0)
+    or init_id itself, and, later, cancels of ids no row holds at those adds' prices with a quantity
+    of at most the add's (at depth 10 they take the init-id row; at depth 3 only init_id's rows,
+    else the -1 index wraps to the last slot), and cancels by those ids themselves."""
+    out = noop_streams(n_env, n_msg, seed, price0=price0, nO=nO)
+    rng = np.random.Generator(np.random.PCG64(seed + 3))
+    for e in range(n_env):
+        rows = []                                   # (side, price, qty, oid)
+        for k in range(n_msg):
+            u = rng.random()
+            if u >= 1 / 6:
+                continue
+            typ0, sd0, q0, p0, o0, tid, t, tn = (int(x) for x in out[e, k])
+            if u < 0.07 or not rows:
+                side = int(rng.choice([-1, 1]))
+                price = price0 - side * int(rng.integers(1, 12))
+                qty = int(rng.integers(5, 50))
+                oid = init_id if rng.random() < 0.2 else init_id - int(rng.integers(7, 21))
+                rows.append((side, price, qty, oid))
+                out[e, k] = (1, side, qty, price, oid, max(tid, 1), t, tn)
+            else:
+                side, price, qty, oid = rows[int(rng.integers(0, len(rows)))]
+                if rng.random() < 0.25:             # by the id itself
+                    out[e, k] = (2, side, int(rng.integers(1, qty + 1)), price, oid, max(tid, 1), t, tn)
+                else:                               # an id no row holds, at the init-id add's price
+                    out[e, k] = (int(rng.choice([2, 3])), side, int(rng.integers(1, qty + 1)), price,
+                                 int(rng.integers(10**6, 2 * 10**6)), max(tid, 1), t, tn)
+    return out
+
+
+EXTREME_VALUES = (-2**31, -2**31 + 1, 2**31 - 2, 2**31 - 1, 0, -1, -2, -22, -23)
+
+
+def extreme_field_streams(n_env, n_msg, seed, p=0.12, price0=1000):
+    """random_streams whose order ids, prices, seconds and nanoseconds are replaced, each with
+    probability p and independently, by int32's extremes and the engine's special values
+    (EXTREME_VALUES: INT32_MIN and its neighbour, INT32_MAX and its neighbour, 0, -1 = the empty
+    marker, -2 = the init id, -22 / -23 = the ends of its range at book_depth 10): the decode
+    classifies on sign, the no-op filter hashes ids and prices, the top-of-book slot compares times.
+    A tenth of the positive quantities become 2^20 .. 2^22, so that 256 slots sum below 2^30 and
+    every quantity sum and difference stays inside int32 (beyond it the oracles have no answer)."""
+    out = random_streams(n_env, n_msg, seed, price0=price0)
+    rng = np.random.Generator(np.random.PCG64(seed + 13))
+    shp = out.shape[:2]
+    vals = np.array(EXTREME_VALUES, dtype=np.int64)
+    for col in (4, 3, 6, 7):
+        hit = rng.random(shp) < p
+        out[..., col] = np.where(hit, rng.choice(vals, size=shp), out[..., col]).astype(np.int32)
+    big = (rng.random(shp) < 0.1) & (out[..., 2] > 0)
+    out[..., 2] = np.where(big, rng.integers(2**20, 2**22 + 1, shp), out[..., 2]).astype(np.int32)
     return out

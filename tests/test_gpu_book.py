@@ -47,6 +47,7 @@ def _run(cfg, msgs, a0, b0, t0, part=True):
         g = g.cpu().numpy()
         bad = np.argwhere(o != g)
         assert bad.size == 0, f"{name} mismatch at {bad[:5].tolist()}: oracle {o[tuple(bad[0])]} gpu {g[tuple(bad[0])]}"
+    return oa, ob, ot, oba, obb
 
 
 @pytest.mark.parametrize("kw", CASES, ids=[str(k) or "default" for k in CASES])

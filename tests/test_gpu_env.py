@@ -86,10 +86,18 @@ def _day(w, mid, seed=11):
     return _DAYS[key]
 
 
-def rollout_parity(cfg, mid=2_000_000, E=64, K=70, seed=11, partitionable=True, day=None):
+def _expect_launch(env, expect):
+    """hftlob_env_launch_info entries (the kernel instantiation the config launches) a case asserts"""
+    info = env.launch_info()
+    for k, v in (expect or {}).items():
+        assert info[k] == v, (k, info)
+
+
+def rollout_parity(cfg, mid=2_000_000, E=64, K=70, seed=11, partitionable=True, day=None, expect=None):
     w = cfg.world_config
     day = _day(w, mid, seed) if day is None else day
     env = MARLEnv(None, cfg, data=day, prng_partitionable=partitionable)
+    _expect_launch(env, expect)
     params = env.default_params
     init = O.init_states(env.cfg_c.lob, env.windows, day.msgs, w, env.layout.init_rec_words)
     assert (init == env._init_states.cpu().numpy()).all()
@@ -541,7 +549,7 @@ def test_multi_agent_per_type_parity(name, agents, changes):
     rollout_parity(_multi_agent_config(name, agents, changes), E=24, K=66)
 
 
-def quiet_rollout_parity(cfg, E=32, T=70, nfix=100):
+def quiet_rollout_parity(cfg, E=32, T=70, nfix=100, expect=None):
     """The persistent rollout's quiet step body (k_env_rollout, per_step = 0: steps 0..T-2 run
     env_step_dev<..., QUIET = true>, which skips the observations, the reward values and the dones,
     and stores only the last row of the best-quote arrays unless an MM type excludes extreme
@@ -556,6 +564,7 @@ def quiet_rollout_parity(cfg, E=32, T=70, nfix=100):
     space)."""
     env = MARLEnv(None, cfg, data=_day(cfg.world_config, 2_000_000))
     assert env.launch_info()["nfix"] == nfix, env.launch_info()
+    _expect_launch(env, expect)
     assert env.default_slices(E) == 0
     params = env.default_params
     keys = torch.from_numpy(np.arange(2 * E, dtype=np.uint32).reshape(E, 2).view(np.int32)).cuda()

@@ -4,6 +4,7 @@ documented JAX split value, and C-oracle vs numpy-oracle agreement."""
 import numpy as np
 import pytest
 
+import book_edges as E
 from golden.book_scenarios import (JORDERBOOK_EXPECT, JORDERBOOK_MSGS, SCENARIOS, jorderbook_init_msgs)
 from hftlob.config import JAXLOB_Configuration
 from hftlob.layout import pack_lob_cfg
@@ -142,3 +143,75 @@ def test_random_cancel_choice_semantics():
     assert R.get_random_id_match(cfg, (1, 2), side, msg) == -1
     out = R.cancel_order(cfg, side, msg, key=(1, 2))
     assert (out[3] == -1).all() and (out[:3] == side[:3]).all()   # slot -1 (empty) -> stays removed
+
+
+def _c_vs_numpy(cfg, rc, msgs, a0, b0, t0, keys=None):
+    """oracle.c's batch == ref_py's scan of every env: books, trades, every message's best quotes"""
+    a, b, t, ba, bb = O.book_process(pack_lob_cfg(cfg), msgs, a0, b0, t0, keys=keys)
+    for i in range(msgs.shape[0]):
+        key = (0, 0) if keys is None else tuple(int(x) for x in keys[i])
+        (ra, rb, rt), rba, rbb = R.scan_save_bidask(rc, msgs[i], a0[i], b0[i], t0[i], key=key)
+        assert (ra == a[i]).all() and (rb == b[i]).all() and (rt == t[i]).all(), f"env {i}"
+        assert (rba == ba[i]).all() and (rbb == bb[i]).all(), f"env {i}: best quotes"
+    return a, b, t
+
+
+@pytest.mark.parametrize("nO,nT", E.EDGE_SIZES, ids=lambda v: str(v))
+def test_c_oracle_vs_numpy_oracle_edge_sizes(nO, nT):
+    """The sizes at which the GPU tier newly compares the HIP engine with oracle.c (the kernels'
+    64-slot register-set boundaries, unequal and tiny sizes): 85-100 % full books, a trade log
+    filled to its last two rows, random then top-of-book messages."""
+    kw = dict(nOrders=nO, nTrades=nT)
+    cfg, rc = JAXLOB_Configuration(**kw), R.default_cfg(**kw)
+    n_env, M = 3, 100
+    a0, b0 = E.full_books(cfg, n_env, seed=3)
+    t0 = E.prefilled_trades(n_env, nT, seed=5)
+    _, _, t = _c_vs_numpy(cfg, rc, E.edge_messages(n_env, M), a0, b0, t0)
+    E.assert_trade_edge(nT, t)
+
+
+@pytest.mark.parametrize("kw", [dict(type_4_interpretation=1), dict(cancel_mode=2)], ids=str)
+@pytest.mark.parametrize("nO", [64, 65, 129])
+def test_c_oracle_vs_numpy_oracle_edge_sizes_modes(nO, kw):
+    """LIM type-4 and the random cancel fallback at register-set boundary sizes"""
+    kw = dict(kw, nOrders=nO, nTrades=nO)
+    cfg, rc = JAXLOB_Configuration(**kw), R.default_cfg(**kw)
+    n_env, M = 2, 100
+    a0, b0 = E.full_books(cfg, n_env, seed=4)
+    keys = np.random.default_rng(nO).integers(0, 2**32, (n_env, 2), dtype=np.uint64).astype(np.uint32)
+    _c_vs_numpy(cfg, rc, E.edge_messages(n_env, M), a0, b0, E.prefilled_trades(n_env, nO, seed=6), keys=keys)
+
+
+@pytest.mark.parametrize("kw", E.INIT_RANGE_CASES, ids=str)
+def test_c_oracle_vs_numpy_oracle_init_id_range(kw):
+    """book_depth / init_id away from 10 / -2: get_init_id_match's id range in both oracles, on
+    streams whose result the setting changes (the default config's books differ)."""
+    kw = dict(kw, nOrders=40, nTrades=30)
+    cfg, rc = JAXLOB_Configuration(**kw), R.default_cfg(**kw)
+    dflt = JAXLOB_Configuration(nOrders=40, nTrades=30)
+    n_env = 3
+    (a0, b0), streams = E.init_range_inputs(cfg, n_env, seed=7)
+    _, e8 = E.empty_book(n_env, cfg)
+    for name, msgs in streams.items():
+        msgs = msgs[:, :150]
+        a, b, _ = _c_vs_numpy(cfg, rc, msgs, a0, b0, e8)
+        if name == "init_range":
+            da, db, _, _, _ = O.book_process(pack_lob_cfg(dflt), msgs, a0, b0, e8)
+            assert (da != a).any() or (db != b).any(), f"{kw} never changed the result on {name}"
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(type_4_interpretation=1), dict(type_4_interpretation=2),
+                                dict(nOrders=16, nTrades=8), dict(nOrders=65, nTrades=65)], ids=str)
+def test_c_oracle_vs_numpy_oracle_extreme_fields(kw):
+    """ids, prices and times at int32's extremes and the engine's special values
+    (streams.extreme_field_streams), quantities inside int32 arithmetic"""
+    cfg, rc = JAXLOB_Configuration(**kw), R.default_cfg(**kw)
+    n_env, M = 4, 150
+    msgs = E.extreme_field_streams(n_env, M, seed=19)
+    for col in (3, 4, 6, 7):
+        assert set(E.EXTREME_VALUES) <= set(msgs[..., col].ravel().tolist()), f"column {col} misses an extreme value"
+    e6, e8 = E.empty_book(n_env, cfg)
+    init = init_book_messages(n_env, seed=2)
+    a0, b0, _, _, _ = O.book_process(pack_lob_cfg(cfg), init, e6, e6, e8, save_best=False)
+    _c_vs_numpy(cfg, rc, msgs, a0, b0, e8)
+    _c_vs_numpy(cfg, rc, msgs, e6, e6, e8)
