@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define HFTLOB_ABI_VERSION 7
+#define HFTLOB_ABI_VERSION 8
 
 #define HFTLOB_OK            0
 #define HFTLOB_EINVAL      (-1)   /* bad config value / unsupported option */
@@ -326,6 +326,23 @@ int hftlob_env_rollout_sampled(const hftlob_env_cfg* cfg /*[host]*/, int n_env, 
                                int32_t* state, const hftlob_step_out* out /*[host] struct*/, int per_step,
                                int n_slices, void* stream);
 
+/* n_steps consecutive MARLEnv.step calls with the caller's keys and actions in ONE persistent
+ * launch: bit for bit the results of
+ *   for t: hftlob_env_step(cfg, n_env, keys + t*n_env*2, actions + t*n_env*action_words, ...)
+ * keys uint32 [n_steps][n_env][2]; actions int32 [n_steps][n_env][action_words] (read only).
+ * per_step as in hftlob_env_rollout_sampled (out->{obs,rewards,done_all,dones,info,obs_raw,msgs,debug}
+ * carry a leading [n_steps]; with per_step == 0 only the last step's outputs are written).
+ * Every env (one wavefront) runs its steps back to back as in the n_slices = 0 launch above (for
+ * 100/100-slot books the book stays in LDS between steps); there is no master-key chain and no env
+ * slicing.  The kernel instantiation is chosen by the rule of the other env launches, so
+ * hftlob_env_launch_info describes this entry point too, apart from key_batch (the step keys
+ * are the caller's).  Like them it neither allocates nor synchronises and can be captured in a
+ * hipGraph. */
+int hftlob_env_rollout_actions(const hftlob_env_cfg* cfg /*[host]*/, int n_env, int n_steps, const uint32_t* keys,
+                               const int32_t* actions, const int32_t* msg_data, const int32_t* init_states,
+                               int32_t* state, const hftlob_step_out* out /*[host] struct*/, int per_step,
+                               void* stream);
+
 /* Creates the library streams / events hftlob_env_rollout_sampled needs for n_slices
  * slices on the device of `stream` (host-only; idempotent). */
 int hftlob_rollout_prepare(int n_slices, void* stream);
@@ -337,9 +354,9 @@ int hftlob_rollout_prepare(int n_slices, void* stream);
  * once); it replaces nothing in the reference, whose XLA compiler sizes its own buffers. */
 int hftlob_env_lds_bytes(const hftlob_env_cfg* cfg /*[host]*/);
 
-/* Which kernel instantiation hftlob_env_step / hftlob_env_rollout_sampled launch for this
- * config, and the launch-derived constants they pass it (host-only, no device call).  Tests
- * use it to assert which code path a parity case ran; it replaces nothing in the reference.
+/* Which kernel instantiation hftlob_env_step / hftlob_env_rollout_sampled /
+ * hftlob_env_rollout_actions launch for this config (key_batch: the sampled rollout only), and
+ * the launch-derived constants they pass it (host-only, no device call).  Tests use it to assert which code path a parity case ran; it replaces nothing in the reference.
  *   slot_sets     register sets per lane (1, 2 or 4: n_orders / n_trades up to 64 / 128 / 256)
  *   nfix          100: the 100/100-slot specialisation; 0: the general-size kernel
  *   random_cancel 1: the cancel_mode 2/3 (get_random_id_match) instantiation

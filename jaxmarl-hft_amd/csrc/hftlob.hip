@@ -3753,6 +3753,77 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout(hftlob_env_cfg c, int n_e
     if ((e == 0) && (lane_id() == 0)) { master_out[0] = mk.a; master_out[1] = mk.b; }
 }
 
+// n_steps MARLEnv.step calls with the CALLER's keys and actions in one launch (hftlob_env_rollout_actions):
+// k_env_rollout's persistent structure (one wave per env, its steps back to back, the book resident
+// in LDS in the 100/100 instantiation, a quiet loop for the steps whose outputs nobody reads, issue
+// priority by projected finish) around the step body's master = false mode: step t reads row t of
+// keys [n_steps][n_env][2] and of actions [n_steps][n_env][action_words] and writes neither.  No
+// master-key chain, so no key batches either (their LDS words after the book stay unused) and no
+// master_out store.  Bit for bit n_steps k_env_step launches over the same rows.
+template <int S, int NFIX, bool RC, bool RA = false>
+__global__ __launch_bounds__(64, 4) void k_env_rollout_actions(hftlob_env_cfg c, int n_env, int n_steps, int per_step,
+                                                            const u32* __restrict__ keys,
+                                                            const i32* __restrict__ actions,
+                                                            const i32* __restrict__ msg_data,
+                                                            const i32* __restrict__ init_states,
+                                                            i32* __restrict__ state, hftlob_step_out out) {
+    one_wave();
+    extern __shared__ __attribute__((aligned(16))) i32 lds[];
+    const int e = blockIdx.x;
+    if (e >= n_env) return;
+    Key mk{0u, 0u};  // (env_step_dev's master-key reference: never read with master = false)
+    // `c` is the first kernel argument: offset 0 of the kernarg segment (constant address space)
+    kcfg_t* kp = (kcfg_t*)__builtin_amdgcn_kernarg_segment_ptr();
+    bool resident = false;  // (the 100/100 instantiation only, as in k_env_rollout)
+    u32 fl = 0;
+#ifndef HFTLOB_NO_BALANCE
+    const unsigned long long bal_r0 = __builtin_amdgcn_s_memrealtime();
+    const u32 bal_hwid = __builtin_amdgcn_s_getreg(0xF804), bal_xcc = __builtin_amdgcn_s_getreg(0x7814);
+    u32 bal_slot;
+    unsigned long long* bal_row = wave_row(bal_hwid, bal_xcc, bal_slot);
+#endif
+    // one step: Q = true for a step whose outputs are not emitted (per_step = 0, not the last step);
+    // the per-step opaque copies of the config and base pointers keep the body's invariants out of
+    // the step loop's preheader (see k_env_rollout)
+    auto step = [&](auto Q, int t) {
+        constexpr bool QT = decltype(Q)::value;
+        const size_t o = per_step ? (size_t)t * n_env : 0;
+        kcfg_t* cp = kp;
+        i32* st = state;
+        const i32* md = msg_data;
+        const i32* is = init_states;
+        asm volatile("" : "+s"(cp), "+s"(st), "+s"(md), "+s"(is));
+        const hftlob_env_cfg& cc = *(const hftlob_env_cfg*)cp;
+        const bool ox = !QT;  // (the optional outputs: written by the emitted steps only)
+        const bool reset = env_step_dev<S, NFIX, RC, RA, QT, /*PK=*/0>(
+            cc, n_env, e, e, keys + (size_t)t * n_env * 2, false, mk,
+            const_cast<i32*>(actions) + (size_t)t * n_env * cc.action_words, md, is, st,
+            out.obs + o * cc.n_agents * cc.obs_stride, out.rewards + o * cc.n_agents, out.done_all + o,
+            out.dones + o * cc.n_agents, ox && out.info ? out.info + o * cc.info_words : nullptr,
+            ox && out.obs_raw ? out.obs_raw + o * cc.n_agents * cc.obs_stride : nullptr,
+            ox && out.msgs ? out.msgs + o * cc.n_msgs * 8 : nullptr,
+            ox && out.debug ? out.debug + o * (size_t)HFTLOB_DEBUG_WORDS(cc.lob.n_trades) : nullptr, lds,
+            NFIX > 0 && resident, NFIX > 0 && t + 1 < n_steps, fl, nullptr, !QT);
+        resident = uni(!reset) != 0;  // (an auto-reset rewrote the record: the next step loads the book from it)
+#ifndef HFTLOB_NO_BALANCE
+        if ((t + 1 < n_steps) && ((t % HFTLOB_BALANCE_EVERY) == 0) && (n_env > HFTLOB_BALANCE_MIN_ENVS))
+            balance_prio(bal_row, bal_slot, bal_r0, t + 1, n_steps - t - 1);
+#endif
+    };
+    int t = 0;
+    if (!per_step) {
+#pragma unroll 1
+        for (; t + 1 < n_steps; ++t) step(std::integral_constant<bool, true>{}, t);
+    }
+#pragma unroll 1
+    for (; t < n_steps; ++t) step(std::integral_constant<bool, false>{}, t);
+#ifndef HFTLOB_NO_BALANCE
+    // the wave is done: its slot's entry becomes a past time, so no neighbour counts it as live
+    if (lane_id() == 0) __hip_atomic_store(bal_row + bal_slot, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
+                                           HFTLOB_PRIO_SCOPE);
+#endif
+}
+
 // ==================================================== K3/K4: PRNG kernels
 #if !defined(HFTLOB_INST)  // (non-template kernels: the main translation unit only)
 __global__ void k_sample_actions(hftlob_env_cfg c, int n_env, const u32* __restrict__ keys, i32* __restrict__ actions) {
@@ -3804,6 +3875,14 @@ __global__ void k_split_keys(int n_env, int n, int part, const u32* __restrict__
 #define HFTLOB_PART8(P) P template __global__ void k_env_rollout<2, 100, false, true>(HFTLOB_ROLL_ARGS); \
                         P template __global__ void k_env_step<2, 100, false, true>(HFTLOB_STEP_ARGS);
 #define HFTLOB_PART9(P) P template __global__ void k_env_rollout<2, 100, false, false, 0>(HFTLOB_ROLL_ARGS);
+// hftlob_env_rollout_actions' kernels: the sampled rollout's set without its key-batch variants
+#define HFTLOB_RACT_ARGS hftlob_env_cfg, int, int, int, const u32*, const i32*, const i32*, const i32*, i32*, hftlob_step_out
+#define HFTLOB_RACT(P, SS, NF, RC, RA) \
+    P template __global__ void k_env_rollout_actions<SS, NF, RC, RA>(HFTLOB_RACT_ARGS);
+#define HFTLOB_PART10(P) HFTLOB_RACT(P, 2, 100, false, false) HFTLOB_RACT(P, 1, 0, false, false)
+#define HFTLOB_PART11(P) HFTLOB_RACT(P, 2, 100, false, true) HFTLOB_RACT(P, 1, 0, true, false)
+#define HFTLOB_PART12(P) HFTLOB_RACT(P, 2, 0, false, false) HFTLOB_RACT(P, 2, 0, true, false)
+#define HFTLOB_PART13(P) HFTLOB_RACT(P, 4, 0, false, false) HFTLOB_RACT(P, 4, 0, true, false)
 #define HFTLOB_NONE
 #if defined(HFTLOB_INST)
 #if HFTLOB_INST == 1
@@ -3824,11 +3903,20 @@ HFTLOB_PART7(HFTLOB_NONE)
 HFTLOB_PART8(HFTLOB_NONE)
 #elif HFTLOB_INST == 9
 HFTLOB_PART9(HFTLOB_NONE)
+#elif HFTLOB_INST == 10
+HFTLOB_PART10(HFTLOB_NONE)
+#elif HFTLOB_INST == 11
+HFTLOB_PART11(HFTLOB_NONE)
+#elif HFTLOB_INST == 12
+HFTLOB_PART12(HFTLOB_NONE)
+#elif HFTLOB_INST == 13
+HFTLOB_PART13(HFTLOB_NONE)
 #endif
 #else  // the main translation unit
 #if !defined(HFTLOB_SINGLE_TU)
 HFTLOB_PART1(extern) HFTLOB_PART2(extern) HFTLOB_PART3(extern) HFTLOB_PART4(extern)
 HFTLOB_PART5(extern) HFTLOB_PART6(extern) HFTLOB_PART7(extern) HFTLOB_PART8(extern) HFTLOB_PART9(extern)
+HFTLOB_PART10(extern) HFTLOB_PART11(extern) HFTLOB_PART12(extern) HFTLOB_PART13(extern)
 #endif
 
 // ================================================================ C ABI
@@ -4230,6 +4318,38 @@ int hftlob_env_rollout_sampled(const hftlob_env_cfg* cfg, int n_env, int key_e0,
             if (!rc) rc = fail(HFTLOB_ELAUNCH, "join event");
     }
     return rc;
+}
+
+int hftlob_env_rollout_actions(const hftlob_env_cfg* cfg, int n_env, int n_steps, const uint32_t* keys,
+                               const int32_t* actions, const int32_t* msg_data, const int32_t* init_states, int32_t* state,
+                               const hftlob_step_out* out, int per_step, void* stream) {
+    int rc = check_env(cfg);
+    if (rc) return rc;
+    if (n_env < 0 || n_steps < 0) return fail(HFTLOB_ESHAPE, "negative n_env / n_steps");
+    if (n_env == 0 || n_steps == 0) return HFTLOB_OK;
+    if (!keys || !actions || !msg_data || !init_states || !state || !out) return fail(HFTLOB_ENULL, "null array");
+    if (!out->obs || !out->rewards || !out->done_all || !out->dones) return fail(HFTLOB_ENULL, "null output");
+    // the instantiation env_rollout_launch selects (hftlob_env_launch_info), without its key-batch variants
+    const int S = slot_sets(cfg->lob.n_orders > cfg->lob.n_trades ? cfg->lob.n_orders : cfg->lob.n_trades);
+    hipStream_t st = (hipStream_t)stream;
+    dim3 g(n_env), b(ENV_BLOCK);
+    const size_t shm = env_shm(cfg);
+    const hftlob_env_cfg kc = kernel_cfg(cfg);
+#define LAUNCH_RACT(SS, NF, RC, RA) hipLaunchKernelGGL((k_env_rollout_actions<SS, NF, RC, RA>), g, b, shm, st, kc, n_env, \
+                                                       n_steps, per_step, keys, actions, msg_data, init_states, state, *out)
+    if (cfg->lob.cancel_mode >= 2) {
+        if (S == 1) LAUNCH_RACT(1, 0, true, false);
+        else if (S == 2) LAUNCH_RACT(2, 0, true, false);
+        else LAUNCH_RACT(4, 0, true, false);
+    } else if (nfix_kernel(cfg)) {
+        if (use_rows_alias(cfg)) LAUNCH_RACT(2, 100, false, true);
+        else LAUNCH_RACT(2, 100, false, false);
+    }
+    else if (S == 1) LAUNCH_RACT(1, 0, false, false);
+    else if (S == 2) LAUNCH_RACT(2, 0, false, false);
+    else LAUNCH_RACT(4, 0, false, false);
+#undef LAUNCH_RACT
+    return launch_status();
 }
 
 int hftlob_sample_actions(const hftlob_env_cfg* cfg, int n_env, const uint32_t* keys, int32_t* actions, void* stream) {

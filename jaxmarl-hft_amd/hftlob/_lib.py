@@ -19,9 +19,10 @@ class LaunchInfo(C.Structure):
                 ("key_batch", C.c_int32)]
 
 LIB_PATH = os.environ.get("HFTLOB_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhftlob.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob_env_reset",
            "hftlob_env_step", "hftlob_env_step_sampled", "hftlob_env_rollout_sampled", "hftlob_rollout_prepare",
+           "hftlob_env_rollout_actions",
            "hftlob_env_lds_bytes", "hftlob_env_launch_info",
            "hftlob_sample_actions", "hftlob_split_keys")
 
@@ -55,6 +56,8 @@ def lib() -> C.CDLL:
     L.hftlob_env_rollout_sampled.argtypes = [C.POINTER(EnvCfg), i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
                                              C.POINTER(StepOut), i32, i32, vp]
     L.hftlob_env_rollout_sampled.restype = i32
+    L.hftlob_env_rollout_actions.argtypes = [C.POINTER(EnvCfg), i32, i32, vp, vp, vp, vp, vp, C.POINTER(StepOut), i32, vp]
+    L.hftlob_env_rollout_actions.restype = i32
     L.hftlob_rollout_prepare.argtypes = [i32, vp]
     L.hftlob_rollout_prepare.restype = i32
     L.hftlob_env_lds_bytes.argtypes = [C.POINTER(EnvCfg)]

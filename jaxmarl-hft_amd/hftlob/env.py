@@ -554,7 +554,59 @@ class MARLEnv:
                   int(per_step), int(n_slices))
         if not per_step:
             return self._results(o, state, E)
-        T = n_steps
+        return self._results_steps(o, state, n_steps, E)
+
+    def _actions_steps(self, actions, T: int, E: int) -> torch.Tensor:
+        """rollout's actions -> the flat int32 [T, E, action_words] buffer of the C ABI: one such
+        tensor, or the per-type list of step with a leading T ([T, E, n_t] Discrete,
+        [T, E, n_t, width] MultiDiscrete)."""
+        if isinstance(actions, torch.Tensor):
+            parts, shapes = [actions], [(T, E, self.action_words)]
+        else:
+            parts = [torch.as_tensor(x) for x in actions]
+            shapes = [(T, E, n) if isinstance(sp, Discrete) else (T, E, n, wd)
+                      for n, wd, sp in zip(self.multi_agent_config.number_of_agents_per_type, self.action_widths,
+                                           self.action_spaces)]
+            if len(parts) != len(shapes):
+                raise ValueError(f"actions must hold one tensor per agent type ({len(shapes)}), got {len(parts)}")
+        for x, shape in zip(parts, shapes):
+            if tuple(x.shape) != shape or x.dtype != torch.int32:
+                raise ValueError(f"actions must be int32 {list(shape)}, got {x.dtype} {list(x.shape)}")
+        if isinstance(actions, torch.Tensor):
+            return actions.to(self.device).contiguous()
+        return torch.cat([x.to(self.device).reshape(T, E, -1) for x in parts], dim=2).contiguous()
+
+    def rollout(self, key: torch.Tensor, state: MultiAgentState, actions, params: MultiAgentParams,
+                per_step: bool = False):
+        """``T`` calls of :meth:`step` with the caller's keys and actions in ONE persistent launch
+        (hftlob_env_rollout_actions): bit for bit ``for t: step(key[t], state, actions[t], params)``,
+        enqueued on the current stream without host synchronisation.  Every env runs its T steps
+        back to back (the 100/100 book stays in LDS between them), so no step waits for the
+        batch's slowest env: the path for replaying recorded or scripted actions and for
+        open-loop action chunks.
+        key: uint32 / int32 [T, E, 2].  actions: int32 [T, E, action_words], or the per-type list
+        :meth:`step` takes with a leading T.  ``state`` is updated in place.
+        per_step=False: obs / rewards / dones / info are the last step's; per_step=True: they
+        carry a leading [T] (the info dict, when enabled, is flattened to [T * E, ...])."""
+        if key.dtype not in (torch.int32, torch.uint32) or key.dim() != 3 or key.shape[2] != 2:
+            raise ValueError("key must be a uint32/int32 tensor [T, E, 2] (one threefry key per step and env)")
+        T, E = int(key.shape[0]), int(key.shape[1])
+        if T < 1:
+            raise ValueError("rollout needs T >= 1 steps")
+        if state.buf.shape[0] != E:
+            raise ValueError(f"key is for {E} envs, the state holds {state.buf.shape[0]}")
+        keys = key.to(self.device).contiguous()
+        acts = self._actions_steps(actions, T, E)
+        o = self._alloc((T, E)) if per_step else self._outputs(E)
+        self._abi("hftlob_env_rollout_actions", C.byref(self.cfg_c), E, T, _lib.ptr(keys), _lib.ptr(acts),
+                  _lib.ptr(params.loaded_params.message_data), _lib.ptr(params.loaded_params.init_states_array),
+                  _lib.ptr(state.buf), C.byref(o["struct"]), int(per_step))
+        if not per_step:
+            return self._results(o, state, E)
+        return self._results_steps(o, state, T, E)
+
+    def _results_steps(self, o, state, T: int, E: int):
+        """_results of per-step buffers [T, E, ...]: a leading [T] on obs / rewards / dones."""
         flat = {k: (v.reshape((T * E,) + tuple(v.shape[2:])) if isinstance(v, torch.Tensor) else v)
                 for k, v in o.items()}
         obs, _, rewards, dones, info = self._results(flat, state, T * E)
