@@ -3855,68 +3855,72 @@ __global__ void k_split_keys(int n_env, int n, int part, const u32* __restrict__
 
 #endif  // !HFTLOB_INST
 
-// ============================================ instantiations (parallel build)
-// The Makefile compiles this file HFTLOB_NPARTS + 1 times: part k (HFTLOB_INST = k) explicitly
-// instantiates its share of the env-step / rollout kernels, the main translation unit (no
-// HFTLOB_INST) declares them extern and holds the small kernels and the C ABI.
+// ============================================ kernel variants (parallel build)
+// The env kernels (k_env_step, k_env_rollout, k_env_rollout_actions) exist in these
+// (S, NFIX, RC, RA) variants and no others: the general-size kernels at 1 / 2 / 4 slot sets without
+// and with the random cancel, and the 100/100 kernel without and with the rows-in-trades layout.
+// env_variant (below) picks one for a config; the declarations and the dispatch come from this list.
+#define HFTLOB_VARIANTS(X)                                              \
+    X(1, 0, false, false) X(2, 0, false, false) X(4, 0, false, false)   \
+    X(1, 0, true, false) X(2, 0, true, false) X(4, 0, true, false)      \
+    X(2, 100, false, false) X(2, 100, false, true)
+constexpr bool is_variant(int S, int NFIX, bool RC, bool RA) {
+#define HFTLOB_X(SS, NF, RC_, RA_) if (S == SS && NFIX == NF && RC == RC_ && RA == RA_) return true;
+    HFTLOB_VARIANTS(HFTLOB_X)
+#undef HFTLOB_X
+    return false;
+}
+// P template k<...>: an explicit instantiation definition (P empty) or declaration (P = extern) of a
+// listed variant's kernel.  The one exception to "a kernel per variant": the sampled rollout at
+// (2, 100, false, false) comes as its two key-batch instantiations, KB = 1 (the metric kernel) and
+// KB = 0, in place of KB = -1 (which is declared with the rest and never launched or defined).
 #define HFTLOB_STEP_ARGS hftlob_env_cfg, int, int, int, const u32*, const u32*, u32*, i32*, const i32*, const i32*, i32*, \
                          hftlob_step_out
 #define HFTLOB_ROLL_ARGS hftlob_env_cfg, int, int, int, int, int, const u32*, u32*, i32*, const i32*, const i32*, i32*, \
                          hftlob_step_out
-#define HFTLOB_STEP(P, SS, NF, RC) P template __global__ void k_env_step<SS, NF, RC, false>(HFTLOB_STEP_ARGS);
-#define HFTLOB_ROLL(P, SS, NF, RC) P template __global__ void k_env_rollout<SS, NF, RC, false>(HFTLOB_ROLL_ARGS);
-#define HFTLOB_PART1(P) P template __global__ void k_env_rollout<2, 100, false, false, 1>(HFTLOB_ROLL_ARGS);
-#define HFTLOB_PART2(P) HFTLOB_STEP(P, 2, 100, false)
-#define HFTLOB_PART3(P) HFTLOB_ROLL(P, 1, 0, false) HFTLOB_STEP(P, 1, 0, false)
-#define HFTLOB_PART4(P) HFTLOB_ROLL(P, 2, 0, false) HFTLOB_STEP(P, 2, 0, false)
-#define HFTLOB_PART5(P) HFTLOB_ROLL(P, 4, 0, false) HFTLOB_STEP(P, 4, 0, false)
-#define HFTLOB_PART6(P) HFTLOB_ROLL(P, 1, 0, true) HFTLOB_STEP(P, 1, 0, true) HFTLOB_ROLL(P, 2, 0, true)
-#define HFTLOB_PART7(P) HFTLOB_STEP(P, 2, 0, true) HFTLOB_ROLL(P, 4, 0, true) HFTLOB_STEP(P, 4, 0, true)
-#define HFTLOB_PART8(P) P template __global__ void k_env_rollout<2, 100, false, true>(HFTLOB_ROLL_ARGS); \
-                        P template __global__ void k_env_step<2, 100, false, true>(HFTLOB_STEP_ARGS);
-#define HFTLOB_PART9(P) P template __global__ void k_env_rollout<2, 100, false, false, 0>(HFTLOB_ROLL_ARGS);
-// hftlob_env_rollout_actions' kernels: the sampled rollout's set without its key-batch variants
 #define HFTLOB_RACT_ARGS hftlob_env_cfg, int, int, int, const u32*, const i32*, const i32*, const i32*, i32*, hftlob_step_out
+#define HFTLOB_LISTED(SS, NF, RC, RA) static_assert(is_variant(SS, NF, RC, RA), "not in HFTLOB_VARIANTS");
+#define HFTLOB_STEP(P, SS, NF, RC, RA) \
+    HFTLOB_LISTED(SS, NF, RC, RA) P template __global__ void k_env_step<SS, NF, RC, RA>(HFTLOB_STEP_ARGS);
+#define HFTLOB_ROLL(P, SS, NF, RC, RA) \
+    HFTLOB_LISTED(SS, NF, RC, RA) P template __global__ void k_env_rollout<SS, NF, RC, RA, -1>(HFTLOB_ROLL_ARGS);
+#define HFTLOB_ROLL_KB(P, KB) \
+    HFTLOB_LISTED(2, 100, false, false) P template __global__ void k_env_rollout<2, 100, false, false, KB>(HFTLOB_ROLL_ARGS);
 #define HFTLOB_RACT(P, SS, NF, RC, RA) \
-    P template __global__ void k_env_rollout_actions<SS, NF, RC, RA>(HFTLOB_RACT_ARGS);
+    HFTLOB_LISTED(SS, NF, RC, RA) P template __global__ void k_env_rollout_actions<SS, NF, RC, RA>(HFTLOB_RACT_ARGS);
+// The Makefile compiles this file HFTLOB_NPARTS + 1 times: part k (HFTLOB_INST = k) instantiates the
+// kernels HFTLOB_PARTk names, the main translation unit (no HFTLOB_INST) declares every listed
+// variant's kernels extern and holds the small kernels and the C ABI.  Which part a kernel builds
+// in only balances the parallel build (part 1 stays the metric kernel alone: `make asm`); a listed
+// kernel that no part instantiates fails the link (-z defs).
+#define HFTLOB_NPARTS 13
+#define HFTLOB_PART1(P) HFTLOB_ROLL_KB(P, 1)
+#define HFTLOB_PART2(P) HFTLOB_STEP(P, 2, 100, false, false)
+#define HFTLOB_PART3(P) HFTLOB_ROLL(P, 1, 0, false, false) HFTLOB_STEP(P, 1, 0, false, false)
+#define HFTLOB_PART4(P) HFTLOB_ROLL(P, 2, 0, false, false) HFTLOB_STEP(P, 2, 0, false, false)
+#define HFTLOB_PART5(P) HFTLOB_ROLL(P, 4, 0, false, false) HFTLOB_STEP(P, 4, 0, false, false)
+#define HFTLOB_PART6(P) HFTLOB_ROLL(P, 1, 0, true, false) HFTLOB_STEP(P, 1, 0, true, false) HFTLOB_ROLL(P, 2, 0, true, false)
+#define HFTLOB_PART7(P) HFTLOB_STEP(P, 2, 0, true, false) HFTLOB_ROLL(P, 4, 0, true, false) HFTLOB_STEP(P, 4, 0, true, false)
+#define HFTLOB_PART8(P) HFTLOB_ROLL(P, 2, 100, false, true) HFTLOB_STEP(P, 2, 100, false, true)
+#define HFTLOB_PART9(P) HFTLOB_ROLL_KB(P, 0)
 #define HFTLOB_PART10(P) HFTLOB_RACT(P, 2, 100, false, false) HFTLOB_RACT(P, 1, 0, false, false)
 #define HFTLOB_PART11(P) HFTLOB_RACT(P, 2, 100, false, true) HFTLOB_RACT(P, 1, 0, true, false)
 #define HFTLOB_PART12(P) HFTLOB_RACT(P, 2, 0, false, false) HFTLOB_RACT(P, 2, 0, true, false)
 #define HFTLOB_PART13(P) HFTLOB_RACT(P, 4, 0, false, false) HFTLOB_RACT(P, 4, 0, true, false)
-#define HFTLOB_NONE
+#define HFTLOB_CAT_(A, B) A##B
+#define HFTLOB_CAT(A, B) HFTLOB_CAT_(A, B)
 #if defined(HFTLOB_INST)
-#if HFTLOB_INST == 1
-HFTLOB_PART1(HFTLOB_NONE)
-#elif HFTLOB_INST == 2
-HFTLOB_PART2(HFTLOB_NONE)
-#elif HFTLOB_INST == 3
-HFTLOB_PART3(HFTLOB_NONE)
-#elif HFTLOB_INST == 4
-HFTLOB_PART4(HFTLOB_NONE)
-#elif HFTLOB_INST == 5
-HFTLOB_PART5(HFTLOB_NONE)
-#elif HFTLOB_INST == 6
-HFTLOB_PART6(HFTLOB_NONE)
-#elif HFTLOB_INST == 7
-HFTLOB_PART7(HFTLOB_NONE)
-#elif HFTLOB_INST == 8
-HFTLOB_PART8(HFTLOB_NONE)
-#elif HFTLOB_INST == 9
-HFTLOB_PART9(HFTLOB_NONE)
-#elif HFTLOB_INST == 10
-HFTLOB_PART10(HFTLOB_NONE)
-#elif HFTLOB_INST == 11
-HFTLOB_PART11(HFTLOB_NONE)
-#elif HFTLOB_INST == 12
-HFTLOB_PART12(HFTLOB_NONE)
-#elif HFTLOB_INST == 13
-HFTLOB_PART13(HFTLOB_NONE)
+#if HFTLOB_INST < 1 || HFTLOB_INST > HFTLOB_NPARTS
+#error "HFTLOB_INST must name one of the parts 1 .. HFTLOB_NPARTS"
 #endif
+HFTLOB_CAT(HFTLOB_PART, HFTLOB_INST)()
 #else  // the main translation unit
 #if !defined(HFTLOB_SINGLE_TU)
-HFTLOB_PART1(extern) HFTLOB_PART2(extern) HFTLOB_PART3(extern) HFTLOB_PART4(extern)
-HFTLOB_PART5(extern) HFTLOB_PART6(extern) HFTLOB_PART7(extern) HFTLOB_PART8(extern) HFTLOB_PART9(extern)
-HFTLOB_PART10(extern) HFTLOB_PART11(extern) HFTLOB_PART12(extern) HFTLOB_PART13(extern)
+#define HFTLOB_X(SS, NF, RC, RA) \
+    HFTLOB_STEP(extern, SS, NF, RC, RA) HFTLOB_ROLL(extern, SS, NF, RC, RA) HFTLOB_RACT(extern, SS, NF, RC, RA)
+HFTLOB_VARIANTS(HFTLOB_X)
+#undef HFTLOB_X
+HFTLOB_ROLL_KB(extern, 1) HFTLOB_ROLL_KB(extern, 0)
 #endif
 
 // ================================================================ C ABI
@@ -4078,69 +4082,82 @@ static bool use_rows_alias(const hftlob_env_cfg* cfg) {
     return nfix_kernel(cfg) && rows_in_trades(*cfg, cfg->lob.n_trades) &&
            4 * lds_map(*cfg, cfg->lob.n_orders, cfg->lob.n_trades, false).words > 160 * 1024 / 16;
 }
-static size_t env_shm(const hftlob_env_cfg* cfg) {
-    const size_t b = 4 * (size_t)lds_map(*cfg, cfg->lob.n_orders, cfg->lob.n_trades, use_rows_alias(cfg)).words;
+
+// The kernel variant a (checked) config launches, one of HFTLOB_VARIANTS: the rule every env launch
+// and hftlob_env_launch_info share.  cancel_mode 2 / 3 takes the random-cancel kernels (general
+// sizes only), else 100/100 configs the 100/100 kernel (it has no MultiDiscrete / fixed_prices
+// path: nfix_kernel), with the rows-in-trades layout where that pays; the others the general-size
+// kernel of their slot sets.  kb: the config derives its rollout step keys in batches (the sampled
+// rollout's KB instantiations at (2, 100, false, false); decided in the kernel elsewhere).
+struct Variant {
+    int S, nfix;
+    bool rc, ra, kb;
+};
+static Variant env_variant(const hftlob_env_cfg* cfg) {
+    Variant v;
+    v.rc = cfg->lob.cancel_mode >= 2;
+    v.nfix = nfix_kernel(cfg) ? 100 : 0;
+    v.S = v.nfix ? 2 : slot_sets(cfg->lob.n_orders > cfg->lob.n_trades ? cfg->lob.n_orders : cfg->lob.n_trades);
+    v.ra = use_rows_alias(cfg);
+    v.kb = kb_ok(*cfg);
+    return v;
+}
+extern "C++" {  // (templates, inside the ABI's extern "C" block)
+template <int S_, int NFIX_, bool RC_, bool RA_> struct VariantT {
+    static constexpr int S = S_, NFIX = NFIX_;
+    static constexpr bool RC = RC_, RA = RA_;
+};
+// f(VariantT<...>{}) for the listed variant v names: the run-time variant as template arguments
+template <class F> static bool with_variant(const Variant& v, F&& f) {
+#define HFTLOB_X(SS, NF, RC, RA) \
+    if (v.S == SS && v.nfix == NF && v.rc == RC && v.ra == RA) return f(VariantT<SS, NF, RC, RA>{}), true;
+    HFTLOB_VARIANTS(HFTLOB_X)
+#undef HFTLOB_X
+    return false;
+}
+static size_t env_shm(const hftlob_env_cfg* cfg, const Variant& v) {
+    const size_t b = 4 * (size_t)lds_map(*cfg, cfg->lob.n_orders, cfg->lob.n_trades, v.ra).words;
     return b < (size_t)HFTLOB_LDS_FLOOR ? (size_t)HFTLOB_LDS_FLOOR : b;
 }
+// One env kernel launch, a wave per env: kernel(V, v) is the kernel's instantiation for the config's
+// variant (V its VariantT), args what follows (cfg, n_env) in its parameters.
+template <class Kernel, class... Args>
+static int env_launch(const hftlob_env_cfg* cfg, int n_env, void* stream, Kernel&& kernel, Args... args) {
+    const Variant v = env_variant(cfg);
+    const hftlob_env_cfg kc = kernel_cfg(cfg);
+    const bool listed = with_variant(v, [&](auto V) {
+        hipLaunchKernelGGL(kernel(V, v), dim3(n_env), dim3(ENV_BLOCK), env_shm(cfg, v), (hipStream_t)stream, kc, n_env,
+                           args...);
+    });
+    return listed ? launch_status() : fail(HFTLOB_ELAUNCH, "no kernel for the config's variant");
+}
+}  // extern "C++"
 
 static int env_step_launch(const hftlob_env_cfg* cfg, int n_env, int key_e0, int key_n, const uint32_t* keys,
                            const uint32_t* key_in, uint32_t* key_out, int32_t* actions, const int32_t* msg_data,
                            const int32_t* init_states, int32_t* state, const hftlob_step_out* out, void* stream) {
     if (!out->obs || !out->rewards || !out->done_all || !out->dones) return fail(HFTLOB_ENULL, "null output");
-    const int S = slot_sets(cfg->lob.n_orders > cfg->lob.n_trades ? cfg->lob.n_orders : cfg->lob.n_trades);
-    hipStream_t st = (hipStream_t)stream;
-    dim3 g(n_env), b(ENV_BLOCK);
-    const size_t shm = env_shm(cfg);
-    const hftlob_env_cfg kc = kernel_cfg(cfg);
-#define LAUNCH_STEP(SS, NF, RC) hipLaunchKernelGGL((k_env_step<SS, NF, RC>), g, b, shm, st, kc, n_env, key_e0, key_n, keys, \
-                                               key_in, key_out, actions, msg_data, init_states, state, *out)
-    if (cfg->lob.cancel_mode >= 2) {  // random cancel fallback: general sizes only
-        if (S == 1) LAUNCH_STEP(1, 0, true);
-        else if (S == 2) LAUNCH_STEP(2, 0, true);
-        else LAUNCH_STEP(4, 0, true);
-    } else if (nfix_kernel(cfg)) {  // the 100/100 kernel has no MultiDiscrete / fixed_prices path
-        if (use_rows_alias(cfg)) hipLaunchKernelGGL((k_env_step<2, 100, false, true>), g, b, shm, st, kc, n_env, key_e0,
-                                                    key_n, keys, key_in, key_out, actions, msg_data, init_states, state, *out);
-        else LAUNCH_STEP(2, 100, false);
-    }
-    else if (S == 1) LAUNCH_STEP(1, 0, false);
-    else if (S == 2) LAUNCH_STEP(2, 0, false);
-    else LAUNCH_STEP(4, 0, false);
-#undef LAUNCH_STEP
-    return launch_status();
+    return env_launch(
+        cfg, n_env, stream,
+        [](auto V, const Variant&) { return k_env_step<decltype(V)::S, decltype(V)::NFIX, decltype(V)::RC, decltype(V)::RA>; },
+        key_e0, key_n, keys, key_in, key_out, actions, msg_data, init_states, state, *out);
 }
 
 // all n_steps of a rollout in one k_env_rollout launch (see there)
 static int env_rollout_launch(const hftlob_env_cfg* cfg, int n_env, int key_e0, int key_n, int n_steps, int per_step,
                               const uint32_t* key_in, uint32_t* key_out, int32_t* actions, const int32_t* msg_data,
                               const int32_t* init_states, int32_t* state, const hftlob_step_out* out, void* stream) {
-    const int S = slot_sets(cfg->lob.n_orders > cfg->lob.n_trades ? cfg->lob.n_orders : cfg->lob.n_trades);
-    hipStream_t st = (hipStream_t)stream;
-    dim3 g(n_env), b(ENV_BLOCK);
-    const size_t shm = env_shm(cfg);
-    const hftlob_env_cfg kc = kernel_cfg(cfg);
-#define LAUNCH_ROLL(SS, NF, RC) hipLaunchKernelGGL((k_env_rollout<SS, NF, RC>), g, b, shm, st, kc, n_env, key_e0, key_n, \
-                                               n_steps, per_step, key_in, key_out, actions, msg_data, init_states, \
-                                               state, *out)
-    if (cfg->lob.cancel_mode >= 2) {
-        if (S == 1) LAUNCH_ROLL(1, 0, true);
-        else if (S == 2) LAUNCH_ROLL(2, 0, true);
-        else LAUNCH_ROLL(4, 0, true);
-    } else if (nfix_kernel(cfg)) {
-        if (use_rows_alias(cfg)) hipLaunchKernelGGL((k_env_rollout<2, 100, false, true>), g, b, shm, st, kc, n_env,
-                                                    key_e0, key_n, n_steps, per_step, key_in, key_out, actions, msg_data,
-                                                    init_states, state, *out);
-        else if (kb_ok(*cfg)) hipLaunchKernelGGL((k_env_rollout<2, 100, false, false, 1>), g, b, shm, st, kc, n_env, key_e0,
-                                                 key_n, n_steps, per_step, key_in, key_out, actions, msg_data,
-                                                 init_states, state, *out);
-        else hipLaunchKernelGGL((k_env_rollout<2, 100, false, false, 0>), g, b, shm, st, kc, n_env, key_e0, key_n, n_steps,
-                                per_step, key_in, key_out, actions, msg_data, init_states, state, *out);
-    }
-    else if (S == 1) LAUNCH_ROLL(1, 0, false);
-    else if (S == 2) LAUNCH_ROLL(2, 0, false);
-    else LAUNCH_ROLL(4, 0, false);
-#undef LAUNCH_ROLL
-    return launch_status();
+    return env_launch(
+        cfg, n_env, stream,
+        [](auto V, const Variant& v) {
+            using T = decltype(V);
+            // (the exception to the list: the 100/100 kernel without alias comes per key-batch mode)
+            if constexpr (T::NFIX > 0 && !T::RA)
+                return v.kb ? k_env_rollout<T::S, T::NFIX, T::RC, T::RA, 1> : k_env_rollout<T::S, T::NFIX, T::RC, T::RA, 0>;
+            else
+                return k_env_rollout<T::S, T::NFIX, T::RC, T::RA, -1>;
+        },
+        key_e0, key_n, n_steps, per_step, key_in, key_out, actions, msg_data, init_states, state, *out);
 }
 
 int hftlob_env_step(const hftlob_env_cfg* cfg, int n_env, const uint32_t* keys, const int32_t* actions,
@@ -4230,22 +4247,21 @@ static int rollout_ctx(int dev, int G, RolloutCtx** out) {
 
 int hftlob_env_lds_bytes(const hftlob_env_cfg* cfg) {
     const int rc = check_env(cfg);
-    return rc ? rc : (int)env_shm(cfg);
+    return rc ? rc : (int)env_shm(cfg, env_variant(cfg));
 }
 
 int hftlob_env_launch_info(const hftlob_env_cfg* cfg, hftlob_launch_info* out) {
     const int rc = check_env(cfg);
     if (rc) return rc;
     if (!out) return fail(HFTLOB_ENULL, "null out");
-    // the selection env_step_launch / env_rollout_launch make
-    const bool rcm = cfg->lob.cancel_mode >= 2, nf = !rcm && nfix_kernel(cfg);
-    out->slot_sets = nf ? 2 : slot_sets(cfg->lob.n_orders > cfg->lob.n_trades ? cfg->lob.n_orders : cfg->lob.n_trades);
-    out->nfix = nf ? 100 : 0;
-    out->random_cancel = rcm ? 1 : 0;
-    out->rows_alias = nf && use_rows_alias(cfg) ? 1 : 0;
-    out->lds_bytes = (int)env_shm(cfg);
+    const Variant v = env_variant(cfg);
+    out->slot_sets = v.S;
+    out->nfix = v.nfix;
+    out->random_cancel = v.rc ? 1 : 0;
+    out->rows_alias = v.ra ? 1 : 0;
+    out->lds_bytes = (int)env_shm(cfg, v);
     out->tick_magic = kernel_cfg(cfg).tick_magic;
-    out->key_batch = kb_ok(*cfg) ? 1 : 0;
+    out->key_batch = v.kb ? 1 : 0;
     return HFTLOB_OK;
 }
 
@@ -4329,27 +4345,12 @@ int hftlob_env_rollout_actions(const hftlob_env_cfg* cfg, int n_env, int n_steps
     if (n_env == 0 || n_steps == 0) return HFTLOB_OK;
     if (!keys || !actions || !msg_data || !init_states || !state || !out) return fail(HFTLOB_ENULL, "null array");
     if (!out->obs || !out->rewards || !out->done_all || !out->dones) return fail(HFTLOB_ENULL, "null output");
-    // the instantiation env_rollout_launch selects (hftlob_env_launch_info), without its key-batch variants
-    const int S = slot_sets(cfg->lob.n_orders > cfg->lob.n_trades ? cfg->lob.n_orders : cfg->lob.n_trades);
-    hipStream_t st = (hipStream_t)stream;
-    dim3 g(n_env), b(ENV_BLOCK);
-    const size_t shm = env_shm(cfg);
-    const hftlob_env_cfg kc = kernel_cfg(cfg);
-#define LAUNCH_RACT(SS, NF, RC, RA) hipLaunchKernelGGL((k_env_rollout_actions<SS, NF, RC, RA>), g, b, shm, st, kc, n_env, \
-                                                       n_steps, per_step, keys, actions, msg_data, init_states, state, *out)
-    if (cfg->lob.cancel_mode >= 2) {
-        if (S == 1) LAUNCH_RACT(1, 0, true, false);
-        else if (S == 2) LAUNCH_RACT(2, 0, true, false);
-        else LAUNCH_RACT(4, 0, true, false);
-    } else if (nfix_kernel(cfg)) {
-        if (use_rows_alias(cfg)) LAUNCH_RACT(2, 100, false, true);
-        else LAUNCH_RACT(2, 100, false, false);
-    }
-    else if (S == 1) LAUNCH_RACT(1, 0, false, false);
-    else if (S == 2) LAUNCH_RACT(2, 0, false, false);
-    else LAUNCH_RACT(4, 0, false, false);
-#undef LAUNCH_RACT
-    return launch_status();
+    return env_launch(
+        cfg, n_env, stream,
+        [](auto V, const Variant&) {
+            return k_env_rollout_actions<decltype(V)::S, decltype(V)::NFIX, decltype(V)::RC, decltype(V)::RA>;
+        },
+        n_steps, per_step, keys, actions, msg_data, init_states, state, *out);
 }
 
 int hftlob_sample_actions(const hftlob_env_cfg* cfg, int n_env, const uint32_t* keys, int32_t* actions, void* stream) {

@@ -185,6 +185,44 @@ def test_env_lds_bytes(L, name, agents, part, kb):
     assert L.hftlob_env_launch_info(C.byref(c), C.byref(info)) == -1
 
 
+_SIZES = [(1, 1), (64, 64), (65, 64), (64, 65), (100, 100), (128, 128), (129, 100), (256, 256)]
+
+
+@pytest.mark.parametrize("fixed_prices", [False, True], ids=["fqc", "fixed_prices"])
+@pytest.mark.parametrize("ep_type", [0, 1])
+@pytest.mark.parametrize("cancel_mode", [0, 2])
+@pytest.mark.parametrize("n_orders,n_trades", _SIZES)
+def test_launch_info_selection_rule(L, n_orders, n_trades, cancel_mode, ep_type, fixed_prices):
+    """hftlob_env_launch_info over the whole kernel-selection rule, restated here: cancel_mode 2 / 3
+    takes the random-cancel kernels; else a 100/100 fixed_steps config without an EXE fixed_prices
+    type takes the 100/100 kernel (two slot sets; the rows-in-trades layout only where the rows' own
+    LDS region would hold the env above 160 KB / 16, which these two-agent configs never reach); the
+    others the general-size kernel of ceil(max(n_orders, n_trades) / 64) slot sets rounded up to
+    1 / 2 / 4.  key_batch is kb_ok of the config at every size."""
+    import dataclasses
+    cfg = builtin_config("2_player_fq_fqc")
+    w = dataclasses.replace(cfg.world_config, nOrders=n_orders, nTrades=n_trades, cancel_mode=cancel_mode,
+                            ep_type=["fixed_steps", "fixed_time"][ep_type])
+    cfg = dataclasses.replace(cfg, world_config=w)
+    if fixed_prices:
+        agents = dict(cfg.dict_of_agents_configs)
+        agents["Execution"] = dataclasses.replace(agents["Execution"], action_space="fixed_prices", n_actions=3,
+                                                  fixed_quant_value=11)
+        cfg = dataclasses.replace(cfg, dict_of_agents_configs=agents)
+    c, _ = pack_env_cfg(cfg, 4, 1000, True)
+    assert (c.lob.n_orders, c.lob.n_trades, c.lob.cancel_mode, c.ep_type) == (n_orders, n_trades, cancel_mode, ep_type)
+    rc = cancel_mode >= 2
+    nfix = not rc and (n_orders, n_trades) == (100, 100) and ep_type == 0 and not fixed_prices
+    n = max(n_orders, n_trades)
+    slot_sets = 2 if nfix else (1 if n <= 64 else 2 if n <= 128 else 4)
+    kb = c.n_agents <= 3 and c.n_action_msgs <= 8 and c.n_types <= 6 and 6 + c.n_agents + c.n_action_msgs <= 16
+    assert kb  # (partitionable keys, two agents: test_env_lds_bytes has configs on the other side of kb_ok)
+    info = _lib.LaunchInfo()
+    assert L.hftlob_env_launch_info(C.byref(c), C.byref(info)) == 0
+    assert (info.slot_sets, info.nfix, info.random_cancel, info.rows_alias, info.key_batch) == \
+        (slot_sets, 100 if nfix else 0, int(rc), 0, int(kb))
+
+
 def tick_magic(d: int) -> int:
     """ceil(2^(31+l) / d), l = ceil(log2 d): the multiplier of tick_floordiv (tools/magic_check.c)"""
     l = (d - 1).bit_length() if d > 1 else 0
