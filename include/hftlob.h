@@ -17,6 +17,9 @@
  *                           msg_array, (asks,bids,trades), N_steps), vmapped;
  *                           with best_asks/best_bids == NULL it is
  *                           scan_through_entire_array (:736-756).
+ *   hftlob_book_process_depth <- :758-789 scan_through_entire_array_save_states, vmapped, with
+ *                           jaxob/jorderbook.py:122-135's get_L2_state of every saved state.
+ *   hftlob_book_depth    <- :1231-1264 get_L2_state, vmapped.
  *   hftlob_env_reset     <- jaxen/marl_env.py:763-770 MARLEnv.reset ->
  *                           reset_env :129-207 (vmapped over envs).
  *   hftlob_env_step      <- jaxen/marl_env.py:775-804 MARLEnv.step (step_env
@@ -50,6 +53,7 @@ extern "C" {
 #define HFTLOB_INFO_AGENT_WORDS 24
 #define HFTLOB_L2_LEVELS   10     /* get_L2_state levels of world debug_mode (marl_env.py:646-651) */
 #define HFTLOB_DEBUG_WORDS(n_trades) (4 * HFTLOB_L2_LEVELS + 8 * (n_trades))
+#define HFTLOB_MAX_DEPTH_LEVELS 16 /* hftlob_book_depth / _process_depth: 4 * n_levels words live in one 64-lane row */
 
 /* ---- engine configuration: JAXLOB_Configuration (jaxob_config.py:12-30) --- */
 typedef struct hftlob_lob_cfg {
@@ -263,6 +267,28 @@ const char* hftlob_last_error(void);
 int hftlob_book_process(const hftlob_lob_cfg* cfg /*[host]*/, int n_env, int n_msg, const uint32_t* keys,
                         const int32_t* msgs, int32_t* asks, int32_t* bids, int32_t* trades,
                         int32_t* best_asks, int32_t* best_bids, void* stream);
+
+/* Batched get_L2_state — replaces jax.vmap(get_L2_state) (JaxOrderBookArrays.py:1231-1264) of
+ * n_env books in HBM, n_levels in 1..HFTLOB_MAX_DEPTH_LEVELS.
+ * depth int32 [n_env][n_levels][4] = [ask_p, ask_q, bid_p, bid_q] per level: unique ask prices
+ *       ascending with -1 read as maxint, unique bid prices descending, missing levels maxint /
+ *       -maxint, the volume summed at the level's price, negative volumes 0. */
+int hftlob_book_depth(const hftlob_lob_cfg* cfg /*[host]*/, int n_env, int n_levels,
+                      const int32_t* asks, const int32_t* bids, int32_t* depth, void* stream);
+
+/* The message scan with the book after every message — replaces
+ * jax.vmap(scan_through_entire_array_save_states) (JaxOrderBookArrays.py:758-789), with the L2
+ * view of jorderbook.process_orders_array_l2 (jorderbook.py:122-135) taken in the same launch.
+ * Processes msgs exactly as hftlob_book_process does (asks / bids / trades updated in place,
+ * keys as there).  For each of the last n_keep messages k (1 <= n_keep <= n_msg) it writes the
+ * state after message k:
+ * depth    [n_env][n_keep][n_levels][4]  (may be NULL: no L2 output; n_levels is then ignored)
+ * all_asks [n_env][n_keep][n_orders][6], all_bids likewise (both or none).
+ * At least one of the outputs must be given.  n_msg == 0 writes nothing. */
+int hftlob_book_process_depth(const hftlob_lob_cfg* cfg /*[host]*/, int n_env, int n_msg, const uint32_t* keys,
+                              const int32_t* msgs, int32_t* asks, int32_t* bids, int32_t* trades,
+                              int n_levels, int n_keep, int32_t* depth,
+                              int32_t* all_asks, int32_t* all_bids, void* stream);
 
 /* Batched MARLEnv.reset — replaces jax.vmap(env.reset, (0, None)):
  * gymnax_exchange/jaxen/marl_env.py:763-770 (reset_env :129-207,

@@ -2977,6 +2977,187 @@ template <int S> DEV void write_debug(const Book<S>& B, i32* dst) {
     store_trades(B.tr, dst + 4 * HFTLOB_L2_LEVELS, B.vt);
 }
 
+// ============================================ K1b: the L2 depth operators
+// get_L2_state with a run-time level count (1 .. HFTLOB_MAX_DEPTH_LEVELS): l2_side's passes and
+// quirks, word for word (bid key -p with int32 wrap, an empty row's -1 a level of its own, fill
+// 1 / -1, the -1 replacements, the volume at the replaced price, negative volumes 0).  outv: the
+// depth row, lane c = word c of [n_levels][ask_p, ask_q, bid_p, bid_q]; the side's words are
+// replaced, the other side's kept.
+template <bool BID, int S>
+DEV i32 depth_side(const Side<S>& s, int R, const Valid<S>& V, i32 maxint, int n_levels, i32 outv) {
+    const int l = lane_id();
+    i32 x[S], q[S];
+    ldcol(s.t, R, FQ, q);
+#pragma unroll
+    for (int r = 0; r < S; ++r) x[r] = BID ? wmul(-1, s.pc[r]) : (s.pc[r] == -1 ? maxint : s.pc[r]);
+    i32 prev = 0;
+    for (int k = 0; k < n_levels; ++k) {
+        i32 m = INT_MAX;
+        lmask any = 0;
+#pragma unroll
+        for (int r = 0; r < S; ++r) {
+            const bool ok = V.v[r] && (k == 0 || x[r] > prev);
+            m = imin_(m, ok ? x[r] : INT_MAX);
+            any |= bal(ok);
+        }
+        i32 lv = wave_min(m);
+        if (any == 0ull) lv = BID ? 1 : -1;
+        else prev = lv;
+        i32 p = BID ? wmul(-1, lv) : lv;
+        p = p == -1 ? (BID ? wsub(0, maxint) : maxint) : p;
+        i32 v = 0;
+#pragma unroll
+        for (int r = 0; r < S; ++r) v = wadd(v, (V.v[r] && s.pc[r] == p) ? q[r] : 0);
+        const i32 vol = imax_(wave_sum(v), 0);
+        const int c = k * 4 + (BID ? 2 : 0);
+        outv = l == c ? p : (l == c + 1 ? vol : outv);
+    }
+    return outv;
+}
+
+// jax.vmap(get_L2_state) of books in memory — JaxOrderBookArrays.py:1231-1264
+template <int S>
+__global__ __launch_bounds__(64) void k_book_depth(hftlob_lob_cfg cfg, int n_env, int n_levels,
+                                                   const i32* __restrict__ asks, const i32* __restrict__ bids,
+                                                   i32* __restrict__ depth) {
+    one_wave();
+    extern __shared__ __attribute__((aligned(16))) i32 lds[];
+    const int e = blockIdx.x;
+    if (e >= n_env) return;
+    const int l = lane_id();
+    Book<S> B;
+    B.c = lobcfg(cfg);
+    book_bind(B, lds);
+    const int R = B.c.nO;
+    load_side<true>(B.a, asks + (size_t)e * R * 6, R, B.vs);
+    load_side<false>(B.b, bids + (size_t)e * R * 6, R, B.vs);
+    i32 v = 0;
+    v = depth_side<false>(B.a, R, B.vs, B.c.maxint, n_levels, v);
+    v = depth_side<true>(B.b, R, B.vs, B.c.maxint, n_levels, v);
+    if (l < 4 * n_levels) depth[(size_t)e * 4 * n_levels + l] = v;
+}
+
+// scan_through_entire_array_save_states — JaxOrderBookArrays.py:758-789 — with the L2 view of
+// jorderbook.process_orders_array_l2 (jorderbook.py:122-135) after every kept message.
+// k_book_process's scan with a chunk loop of its own: the pre-pass (decode_msgs, chunk_noops) and the
+// handlers are shared, but every message of the chunk, skipped ones included, passes through the loop
+// so that each of the last n_keep gets its output rows (a skipped message repeats the rows before it).
+// The handlers write through: a slot write reaches the LDS table and the register price column
+// before the handler returns (stu / st6 / clr6 / col_set; only the best-quote record's lane fill
+// waits for the chunk's end, and nothing here reads it), so the sides can be viewed and stored after
+// any message.
+// The depth row stays in one VGPR (lane c = word c) and a side's words are recomputed only after a
+// message that can have changed the side:
+//   a cancel: its own side; an add: its own side (the handler kind, i.e. after the type-4 flip;
+//   evictions are on the own side), and the other side too unless the trade count proves that it
+//   matched nothing: ntr known (>= 0), below n_trades (a full log's count stays put) and unchanged,
+//   with a message time != -1 (match_order does not count a trade whose time is -1).
+// (-DHFTLOB_DEPTH_BOTH, A/B builds only: both sides after every processed message)
+template <int S, bool RC>
+__global__ __launch_bounds__(64) void k_book_process_depth(hftlob_lob_cfg cfg, int n_env, int n_msg,
+                                                           const u32* __restrict__ keys, const i32* __restrict__ msgs,
+                                                           i32* __restrict__ asks, i32* __restrict__ bids,
+                                                           i32* __restrict__ trades, int n_levels, int n_keep,
+                                                           i32* __restrict__ depth, i32* __restrict__ all_asks,
+                                                           i32* __restrict__ all_bids) {
+    one_wave();
+    extern __shared__ __attribute__((aligned(16))) i32 lds[];
+    const int e = blockIdx.x;
+    if (e >= n_env) return;
+    const int l = lane_id();
+    Book<S> B;
+    B.c = lobcfg(cfg);
+    book_bind(B, lds);
+    const int R = B.c.nO;
+    i32* ga = asks + (size_t)e * R * 6;
+    i32* gb = bids + (size_t)e * R * 6;
+    i32* gt = trades + (size_t)e * B.c.nT * 8;
+    B.fl = load_side<true>(B.a, ga, R, B.vs) | load_side<false>(B.b, gb, R, B.vs) | F_STALE_A | F_STALE_B | STALE_ANY;
+    B.fl |= slow_bit(B.fl);
+    load_trades(B.tr, gt, B.vt);
+    {  // the loaded log's free-row prefix (see Book::ntr)
+        lmask fr[S], bad = 0;
+#pragma unroll
+        for (int r = 0; r < S; ++r) fr[r] = B.vt.m[r] & bal(B.tr.get(4, r) == -1);
+        const int first = first_slot(fr, B.c.nT);
+#pragma unroll
+        for (int r = 0; r < S; ++r) bad |= B.vt.m[r] & ~fr[r] & bal(r * 64 + l >= first);
+        B.ntr = bad == 0ull ? first : -1;
+    }
+    if (RC) {
+        B.ek = Key{keys[2 * e], keys[2 * e + 1]};
+        B.nmsg = n_msg;
+        B.part = cfg.prng_partitionable;
+    }
+    const int first_kept = n_msg - n_keep;  // (0 <= first_kept < n_msg: checked by the host)
+    const int dw = 4 * n_levels;            // depth words per row (<= 64)
+    i32* gd = depth ? depth + (size_t)e * n_keep * dw : nullptr;
+    i32* gsa = all_asks ? all_asks + (size_t)e * n_keep * R * 6 : nullptr;
+    i32* gsb = all_asks ? all_bids + (size_t)e * n_keep * R * 6 : nullptr;
+    i32 dv = 0;       // the depth row
+    u32 dirty = 3u;   // sides whose words of dv are out of date: 1 asks, 2 bids
+    const i32* gm = msgs + (size_t)e * n_msg * 8;
+    int4 nx = make_int4(0, 0, 0, 0), ny = nx;  // message rows, loaded one chunk ahead
+    if (l < n_msg) {
+        ld_msg(gm + l * 8, nx, ny);
+    }
+    for (int base = 0; base < n_msg; base += 64) {
+        const int row = base + l;
+        int4 x = nx, y = ny;
+        nx = make_int4(0, 0, 0, 0);
+        ny = nx;
+        if (row + 64 < n_msg) {  // the next chunk's loads land while this one runs
+            ld_msg(gm + (row + 64) * 8, nx, ny);
+        }
+        decode_msgs(B.c, x, y);
+        const int cnt = uni(imin_(64, n_msg - base));
+        const lmask live = cnt >= 64 ? ~0ull : (1ull << cnt) - 1ull;
+        i32 hf;
+        const lmask skip = chunk_noops<RC>(B, x, y, cnt, hf) & live;
+        const i32 hx = x.x | hf;
+        refresh_best<false>(B);
+        B.a.rm = B.b.rm = 0ull;  // (the handlers' best-quote record: written, never read here)
+        B.a.rp = B.a.rq = B.b.rp = B.b.rq = 0;
+        for (int k = 0; k < cnt; ++k) {
+            if (!((skip >> k) & 1ull)) {
+                const i32 h = rdl(hx, k), d2 = rdl(x.z, k), d3 = rdl(x.w, k), d4 = rdl(y.x, k), d5 = rdl(y.y, k),
+                          d6 = rdl(y.z, k), d7 = rdl(y.w, k);
+                const i32 ntr0 = B.ntr;
+                if (RC) B.mi = base + k;
+                if ((i32)B.fl >= 0) process_msg_<false, RC>(B, (u32)k, h, x.y, d2, d3, d4, d5, d6, d7);  // (!F_SLOW)
+                else process_msg_<true, RC>(B, (u32)k, h, x.y, d2, d3, d4, d5, d6, d7);
+                refresh_best(B, (u32)k);
+#ifdef HFTLOB_DEPTH_BOTH
+                (void)ntr0;
+                dirty = 3u;
+#else
+                const i32 kind = h & H_KIND;
+                const bool add = kind <= H_BID;
+                const bool no_trade = (ntr0 >= 0) & (ntr0 < B.c.nT) & (B.ntr == ntr0) & (d6 != -1);
+                dirty |= ((kind == H_ASK) | (kind == H_CNL_ASK)) ? 1u : 2u;
+                if (add & !no_trade) dirty = 3u;
+#endif
+            }
+            const int j = base + k - first_kept;
+            if (j >= 0) {
+                if (gd) {
+                    if (dirty & 1u) dv = depth_side<false>(B.a, R, B.vs, B.c.maxint, n_levels, dv);
+                    if (dirty & 2u) dv = depth_side<true>(B.b, R, B.vs, B.c.maxint, n_levels, dv);
+                    dirty = 0u;
+                    if (l < dw) gd[(size_t)j * dw + l] = dv;
+                }
+                if (gsa) {
+                    store_side(B.a, gsa + (size_t)j * R * 6, R, B.vs);
+                    store_side(B.b, gsb + (size_t)j * R * 6, R, B.vs);
+                }
+            }
+        }
+    }
+    store_side(B.a, ga, R, B.vs);
+    store_side(B.b, gb, R, B.vs);
+    store_trades(B.tr, gt, B.vt);
+}
+
 // ====================================================== K2: fused env step
 // MARLEnv.step — marl_env.py:775-804 (step_env :211-709, auto-reset select)
 #define MAX_AGENT_ROWS 128
@@ -3970,6 +4151,60 @@ int hftlob_book_process(const hftlob_lob_cfg* cfg, int n_env, int n_msg, const u
     const size_t shm = 4 * (size_t)book_words(cfg->n_orders, cfg->n_trades);
 #define LAUNCH_BOOK(SS, RC) hipLaunchKernelGGL((k_book_process<SS, RC>), g, b, shm, st, *cfg, n_env, n_msg, keys, msgs, \
                                                asks, bids, trades, best_asks, best_bids)
+    if (rc_) {
+        if (S == 1) LAUNCH_BOOK(1, true);
+        else if (S == 2) LAUNCH_BOOK(2, true);
+        else LAUNCH_BOOK(4, true);
+    } else {
+        if (S == 1) LAUNCH_BOOK(1, false);
+        else if (S == 2) LAUNCH_BOOK(2, false);
+        else LAUNCH_BOOK(4, false);
+    }
+#undef LAUNCH_BOOK
+    return launch_status();
+}
+
+int hftlob_book_depth(const hftlob_lob_cfg* cfg, int n_env, int n_levels, const int32_t* asks, const int32_t* bids,
+                      int32_t* depth, void* stream) {
+    int rc = check_lob(cfg);
+    if (rc) return rc;
+    if (n_env < 0) return fail(HFTLOB_ESHAPE, "negative size");
+    if (n_levels < 1 || n_levels > HFTLOB_MAX_DEPTH_LEVELS) return fail(HFTLOB_ESHAPE, "n_levels out of 1..16");
+    if (n_env == 0) return HFTLOB_OK;
+    if (!asks || !bids || !depth) return fail(HFTLOB_ENULL, "null array");
+    const int S = slot_sets(cfg->n_orders > cfg->n_trades ? cfg->n_orders : cfg->n_trades);
+    hipStream_t st = (hipStream_t)stream;
+    dim3 g(n_env), b(ENV_BLOCK);
+    const size_t shm = 4 * (size_t)book_words(cfg->n_orders, cfg->n_trades);
+#define LAUNCH_DEPTH(SS) hipLaunchKernelGGL((k_book_depth<SS>), g, b, shm, st, *cfg, n_env, n_levels, asks, bids, depth)
+    if (S == 1) LAUNCH_DEPTH(1);
+    else if (S == 2) LAUNCH_DEPTH(2);
+    else LAUNCH_DEPTH(4);
+#undef LAUNCH_DEPTH
+    return launch_status();
+}
+
+int hftlob_book_process_depth(const hftlob_lob_cfg* cfg, int n_env, int n_msg, const uint32_t* keys, const int32_t* msgs,
+                              int32_t* asks, int32_t* bids, int32_t* trades, int n_levels, int n_keep, int32_t* depth,
+                              int32_t* all_asks, int32_t* all_bids, void* stream) {
+    int rc = check_lob(cfg);
+    if (rc) return rc;
+    if (n_env < 0 || n_msg < 0) return fail(HFTLOB_ESHAPE, "negative size");
+    if (depth && (n_levels < 1 || n_levels > HFTLOB_MAX_DEPTH_LEVELS)) return fail(HFTLOB_ESHAPE, "n_levels out of 1..16");
+    if (n_msg > 0 && (n_keep < 1 || n_keep > n_msg)) return fail(HFTLOB_ESHAPE, "n_keep out of 1..n_msg");
+    if (!depth && !all_asks && !all_bids) return fail(HFTLOB_ENULL, "no output: depth and all_asks / all_bids are NULL");
+    if ((all_asks == nullptr) != (all_bids == nullptr)) return fail(HFTLOB_ENULL, "all_asks/all_bids: both or none");
+    if (n_env == 0 || n_msg == 0) return HFTLOB_OK;
+    if (!asks || !bids || !trades || !msgs) return fail(HFTLOB_ENULL, "null array");
+    const bool rc_ = cfg->cancel_mode >= 2;
+    if (rc_ && !keys) return fail(HFTLOB_ENULL, "keys required for cancel_mode 2/3");
+    const int S = slot_sets(cfg->n_orders > cfg->n_trades ? cfg->n_orders : cfg->n_trades);
+    hipStream_t st = (hipStream_t)stream;
+    dim3 g(n_env), b(ENV_BLOCK);
+    const size_t shm = 4 * (size_t)book_words(cfg->n_orders, cfg->n_trades);
+    if (!depth) n_levels = 1;  // (ignored without an L2 output)
+#define LAUNCH_BOOK(SS, RC) hipLaunchKernelGGL((k_book_process_depth<SS, RC>), g, b, shm, st, *cfg, n_env, n_msg, keys, \
+                                               msgs, asks, bids, trades, n_levels, n_keep, depth, all_asks, all_bids)
     if (rc_) {
         if (S == 1) LAUNCH_BOOK(1, true);
         else if (S == 2) LAUNCH_BOOK(2, true);

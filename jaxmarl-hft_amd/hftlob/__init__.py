@@ -3,7 +3,9 @@
 Host package (PyTorch-ROCm tensors) over ``libhftlob.so`` (HIP, gfx950).
 Drop-in names follow biiiipy/JaxMARL-HFT (``gymnax_exchange.jaxob`` /
 ``gymnax_exchange.jaxen``): config dataclasses, ``MARLEnv``, and the
-engine operators ``scan_through_entire_array[_save_bidask]``.
+engine operators ``scan_through_entire_array[_save_bidask|_save_states]`` and
+``get_L2_state`` (``hftlob.engine``), and the ``OrderBook`` object of
+``jaxob/jorderbook.py`` (``hftlob.orderbook``).
 """
 from .config import (JAXLOB_Configuration, MarketMaking_EnvironmentConfig, Execution_EnvironmentConfig,
                      World_EnvironmentConfig, MultiAgentConfig, CONFIG_OBJECT_DICT)

@@ -20,7 +20,8 @@ class LaunchInfo(C.Structure):
 
 LIB_PATH = os.environ.get("HFTLOB_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhftlob.so")
 ABI_VERSION = 8
-EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob_env_reset",
+EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob_book_depth",
+           "hftlob_book_process_depth", "hftlob_env_reset",
            "hftlob_env_step", "hftlob_env_step_sampled", "hftlob_env_rollout_sampled", "hftlob_rollout_prepare",
            "hftlob_env_rollout_actions",
            "hftlob_env_lds_bytes", "hftlob_env_launch_info",
@@ -47,6 +48,10 @@ def lib() -> C.CDLL:
     L.hftlob_last_error.restype = C.c_char_p
     L.hftlob_book_process.argtypes = [C.POINTER(LobCfg), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.hftlob_book_process.restype = i32
+    L.hftlob_book_depth.argtypes = [C.POINTER(LobCfg), i32, i32, vp, vp, vp, vp]
+    L.hftlob_book_depth.restype = i32
+    L.hftlob_book_process_depth.argtypes = [C.POINTER(LobCfg), i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.hftlob_book_process_depth.restype = i32
     L.hftlob_env_reset.argtypes = [C.POINTER(EnvCfg), i32, vp, vp, vp, vp, C.POINTER(StepOut), vp]
     L.hftlob_env_reset.restype = i32
     L.hftlob_env_step.argtypes = [C.POINTER(EnvCfg), i32, vp, vp, vp, vp, vp, C.POINTER(StepOut), vp]
