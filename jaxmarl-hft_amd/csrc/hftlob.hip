@@ -1968,6 +1968,82 @@ DEV void put_row(i32* lds_rows, int row, i32 f0, i32 f1, i32 f2, i32 f3, i32 f4,
     if (l < 8) lds_rows[row * 8 + l] = v;
 }
 
+// Row sinks: the agent functions below put the step's message rows [cancels C][actions A] with
+// put_row(rows, ...), and `rows` is one of two things.  An i32*: the LDS staging area (the
+// general-size and rows-alias kernels; filter_rows, the shuffle and chunk 0 read it back).  A
+// RegRows*: lane r holds row r as the two int4 halves chunk 0 of the book loop consumes (the
+// 100/100 kernel without the rows alias, C + A <= 64: reg_rows_ok), with the book columns
+// getCancelMsgs and masked_best read, loaded once per step (one wait).
+template <int S>
+struct RegRows {
+    int4 x, y;                                          // lane r: row r
+    i32 meta;                                           // the lane's filter groups (agent(), filter_regs)
+    i32 at[S], aq[S], ao[S], bt[S], bq[S], bo[S];       // FTID / FQ / FOID of the asks and the bids
+    // The fields that are regular over rows are set lane-wise, not per row: here the cancel lanes'
+    // type and time words (an unused cancel slot is the row (2, side, 0, 0, 0, 0, t, tns)), in
+    // agent() an agent's trader id and delayed time words over its action lanes, in cancel_regs the
+    // side over an agent's cancel lanes.  The placeholder id is not stored: every action lane gets
+    // its order id after the filter.
+    DEV void init(const i32* ta, const i32* tb, int R, int C, i32 t, i32 tns) {
+        const int l = lane_id();
+        const bool cl = l < C;
+        x = make_int4(cl ? 2 : 0, 0, 0, 0);
+        y = make_int4(0, 0, cl ? t : 0, cl ? tns : 0);
+        meta = l | l << 8;
+        ldcol(ta, R, FTID, at); ldcol(ta, R, FQ, aq); ldcol(ta, R, FOID, ao);
+        ldcol(tb, R, FTID, bt); ldcol(tb, R, FQ, bq); ldcol(tb, R, FOID, bo);
+    }
+    // an action row: its type, side, quantity and price (lane-indexed selects: the float-derived
+    // fields are uniform values in VGPRs, which a v_writelane would first move to the scalar unit);
+    // f4 .. f7 are the agent's regular fields, see agent()
+    DEV void put(int row, i32 f0, i32 f1, i32 f2, i32 f3, i32, i32, i32, i32) {
+        const bool m = lane_id() == row;
+        x.x = m ? f0 : x.x; x.y = m ? f1 : x.y; x.z = m ? f2 : x.z; x.w = m ? f3 : x.w;
+    }
+    // one agent's lanes: n action rows from arow (trader id tid, message time t / tns) and n cancel
+    // rows from crow.  meta: first lane of the lane's own group | of the agent's other group << 8 |
+    // (n - 1) << 16 (n = 1 / 2 / 4)
+    DEV void agent(int arow, int crow, int n, i32 tid, i32 t, i32 tns) {
+        const int l = lane_id();
+        const bool ia = (u32)(l - arow) < (u32)n, ic = (u32)(l - crow) < (u32)n;
+        y.y = ia ? tid : y.y; y.z = ia ? t : y.z; y.w = ia ? tns : y.w;
+        const i32 ma = arow | crow << 8 | (n - 1) << 16, mc = crow | arow << 8 | (n - 1) << 16;
+        meta = ia ? ma : (ic ? mc : meta);
+    }
+};
+template <int S>
+DEV void put_row(RegRows<S>* r, int row, i32 f0, i32 f1, i32 f2, i32 f3, i32 f4, i32 f5, i32 f6, i32 f7) {
+    r->put(row, f0, f1, f2, f3, f4, f5, f6, f7);
+}
+template <class T> struct is_reg_rows { static constexpr bool value = false; };
+template <int S> struct is_reg_rows<RegRows<S>*> { static constexpr bool value = true; };
+template <bool REG, int S> DEV auto row_sink(RegRows<S>& regs, i32* lds_rows) {
+    if constexpr (REG) return &regs;
+    else return lds_rows;
+}
+// getCancelMsgs into an agent's cancel lanes row0 .. row0 + size - 1 of one side, from the step's
+// column registers: the first `size` orders of the agent in slot order; the other lanes stay the
+// unused slot's row
+template <int S>
+DEV void cancel_regs(RegRows<S>& sink, const i32 (&tid)[S], const i32 (&q)[S], const i32 (&o)[S], const i32 (&p)[S],
+                     const Valid<S>& V, i32 agent, int size, i32 side, int row0) {
+    const int l = lane_id();
+    sink.x.y = (u32)(l - row0) < (u32)size ? side : sink.x.y;
+    int n = 0;
+#pragma unroll
+    for (int r = 0; r < S; ++r) {
+        lmask bm = V.m[r] & bal(tid[r] == agent);
+        while (bm && n < size) {
+            const int ln = (int)__builtin_ctzll(bm);
+            bm &= bm - 1;
+            const bool m = l == row0 + n;
+            sink.x.z = m ? rdl(q[r], ln) : sink.x.z; sink.x.w = m ? rdl(p[r], ln) : sink.x.w;
+            sink.y.x = m ? rdl(o[r], ln) : sink.y.x; sink.y.y = m ? agent : sink.y.y;
+            ++n;
+        }
+    }
+}
+
 // getCancelMsgs — JaxOrderBookArrays.py:827-853
 template <int S>
 DEV void cancel_rows(const Side<S>& s, int R, const Valid<S>& V, i32 agent, int size, i32 side, i32 t, i32 tns,
@@ -2034,19 +2110,59 @@ DEV void filter_rows(i32* lds_rows, int arow, int crow, i32* scratch) {
     }
     wave_sync();
 }
+// The same rule over rows held in registers (RegRows), every agent of the step at once.  A lane
+// knows its own group (an agent's action rows or its cancel rows: n = 1 / 2 / 4 lanes) and the
+// agent's other group from its meta word.  It reads the other group's n prices through rotated
+// ds_bpermute gathers (matched: one equals its own, which is not 0), ranks itself inside its group
+// from the ballot of the matched lanes, and the k-th matched quantities meet in the agent's k-th
+// action lane: the matched rows send theirs there with ds_permute (a lane nothing is sent to reads
+// 0, the zero padding), the lane forms rel[k], and every row gathers the rel of its rank.  The rows
+// that send nothing address lane 0, a cancel lane, which no rank reads.  No LDS memory, no
+// wave_sync().  The 100/100 kernel has no fixed_prices type: n <= 4 (MM 2, EXE 1 / 2 / 4).
+template <int S>
+DEV void filter_regs(RegRows<S>& s, int C) {
+    const int l = lane_id();
+    const int own = s.meta & 0xFF, oth = (s.meta >> 8) & 0xFF, g1 = s.meta >> 16, off = l - own;
+    const i32 p = s.x.w, q = s.x.z;
+    bool hit = false;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) hit |= __builtin_amdgcn_ds_bpermute((oth + ((off + r) & g1)) << 2, p) == p;
+    const bool matched = hit & (p != 0);
+    const lmask M = bal(matched);
+    const u32 grp = (u32)(M >> own) & ((2u << g1) - 1u);  // the matched rows of the lane's group
+    const int mb = __builtin_popcount(grp & ((1u << off) - 1u));
+    const int rank = matched ? mb : __builtin_popcount(grp) + off - mb;  // (unmatched rows rank after the matched)
+    const bool is_a = l >= C;
+    const int slot = ((is_a ? own : oth) + rank) << 2;
+    const i32 av = __builtin_amdgcn_ds_permute((matched & is_a) ? slot : 0, q);
+    const i32 cv = __builtin_amdgcn_ds_permute((matched & !is_a) ? slot : 0, q);
+    const i32 nq = wsub(q, __builtin_amdgcn_ds_bpermute(slot, cv >= av ? av : 0));
+    if (is_a & (nq == 0)) {
+        s.x = make_int4(0, 0, 0, 0);
+        s.y = s.x;
+    } else {
+        s.x.z = nq;
+    }
+}
 
 // MM _getActionMsgs_fixedQuant — mm_env.py:970-1118
 // best ask / bid of the book with the agent's own orders masked out (get_best_bid_and_ask
 // over the masked sides, mm_env.py:979-997), floored to the tick; an empty side falls back
 // to the last recorded best quotes.  Returns empty_book.
-template <int S>
-DEV bool masked_best(const hftlob_env_cfg& c, Book<S>& B, i32 tid, i32 last_ba, i32 last_bb, i32& ba, i32& bb) {
+template <int S, class Rows>
+DEV bool masked_best(const hftlob_env_cfg& c, Book<S>& B, const Rows lds_rows, i32 tid, i32 last_ba, i32 last_bb, i32& ba,
+                     i32& bb) {
     const i32 tick = c.tick_size;
     i32 mn = INT_MAX, mx = INT_MIN, at_[S], bt_[S];
     const i32 (&ap_)[S] = B.a.pc;
     const i32 (&bp_)[S] = B.b.pc;
-    ldcol(B.a.t, B.c.nO, FTID, at_);
-    ldcol(B.b.t, B.c.nO, FTID, bt_);
+    if constexpr (is_reg_rows<Rows>::value) {  // (the step's column registers)
+#pragma unroll
+        for (int r = 0; r < S; ++r) { at_[r] = lds_rows->at[r]; bt_[r] = lds_rows->bt[r]; }
+    } else {
+        ldcol(B.a.t, B.c.nO, FTID, at_);
+        ldcol(B.b.t, B.c.nO, FTID, bt_);
+    }
 #pragma unroll
     for (int r = 0; r < S; ++r) {
         const i32 pa = (B.vs.v[r] && at_[r] != tid) ? ap_[r] : -1;
@@ -2063,13 +2179,13 @@ DEV bool masked_best(const hftlob_env_cfg& c, Book<S>& B, i32 tid, i32 last_ba, 
     if (empty) { bb = last_bb; ba = last_ba; }
     return empty;
 }
-template <int S>
+template <int S, class Rows>
 DEV void mm_fixed_quant(const hftlob_env_cfg& c, const hftlob_agent_type_cfg& tc, Book<S>& B, const i32* st, i32 tid,
-                        i32 action, i32 wt0, i32 wt1, i32 last_ba, i32 last_bb, i32* lds_rows, int row, ActX& x) {
+                        i32 action, i32 wt0, i32 wt1, i32 last_ba, i32 last_bb, Rows lds_rows, int row, ActX& x) {
     if (tc.fixed_action_setting) action = tc.fixed_action;
     const i32 tick = c.tick_size;
     i32 ba, bb;
-    const bool empty = masked_best(c, B, tid, last_ba, last_bb, ba, bb);
+    const bool empty = masked_best(c, B, lds_rows, tid, last_ba, last_bb, ba, bb);
     const float hsp = fmaxf(i2f(wsub(ba, bb)) / 2.0f, (float)tick / 2.0f);
     const float hs = (tick_ffloordiv(c, hsp) + 1.0f) * (float)tick;
     float bo, ao;
@@ -2118,9 +2234,9 @@ DEV void mm_fixed_quant(const hftlob_env_cfg& c, const hftlob_agent_type_cfg& tc
 DEV i32 f2i_sat(float f) {  // XLA f32 -> s32 convert: saturating, NaN -> 0
     return f != f ? 0 : (f >= 2147483648.0f ? INT_MAX : (f <= -2147483648.0f ? INT_MIN : (i32)f));
 }
-template <int S>
+template <int S, class Rows>
 DEV void mm_other_actions(const hftlob_env_cfg& c, const hftlob_agent_type_cfg& tc, Book<S>& B, const i32* st, i32 tid,
-                          i32 action, i32 wt0, i32 wt1, i32 last_ba, i32 last_bb, i32 step, i32 init_t0, i32* lds_rows,
+                          i32 action, i32 wt0, i32 wt1, i32 last_ba, i32 last_bb, i32 step, i32 init_t0, Rows lds_rows,
                           int row, ActX& x) {
     if (tc.fixed_action_setting) action = tc.fixed_action;
     const i32 tick = c.tick_size, inv = st[2], fq = tc.fixed_quant_value;
@@ -2134,7 +2250,7 @@ DEV void mm_other_actions(const hftlob_env_cfg& c, const hftlob_agent_type_cfg& 
     i32 bp, ap, bq, aq, bdist = 0, adist = 0, bpost = 0, apost = 0;
     if (kind == HFTLOB_MM_ACT_BOB_RL || kind == HFTLOB_MM_ACT_BOB_STRATEGY || kind == HFTLOB_MM_ACT_AVST) {
         i32 ba, bb;
-        const bool empty = masked_best(c, B, tid, last_ba, last_bb, ba, bb);
+        const bool empty = masked_best(c, B, lds_rows, tid, last_ba, last_bb, ba, bb);
         if (kind == HFTLOB_MM_ACT_BOB_RL) {  // :1474-1561; tables bid v0 + (+k, -k, ...) / ask v0 - ...
             const i32 v0 = tc.bob_v0, d = (ai & 1) ? (ai + 1) / 2 : -(ai / 2);
             bq = wmul(wadd(v0, d), fq);
@@ -2210,8 +2326,9 @@ DEV void mm_other_actions(const hftlob_env_cfg& c, const hftlob_agent_type_cfg& 
 }
 
 // MM _getActionMsgs_directional_trading — mm_env.py:1810-1865
+template <class Rows>
 DEV void mm_directional(const hftlob_env_cfg& c, const hftlob_agent_type_cfg& tc, i32 tid, i32 action, i32 wt0, i32 wt1,
-                        i32 last_ba, i32 last_bb, i32* lds_rows, int row, ActX& x) {
+                        i32 last_ba, i32 last_bb, Rows lds_rows, int row, ActX& x) {
     const i32 tick = c.tick_size;
     const i32 ba = wmul(tick_floordiv(c, last_ba), tick), bb = wmul(tick_floordiv(c, last_bb), tick);
     const int ai = action < 0 ? imax_(action + 3, 0) : (action > 2 ? 2 : action);
@@ -2225,8 +2342,9 @@ DEV void mm_directional(const hftlob_env_cfg& c, const hftlob_agent_type_cfg& tc
 
 // EXE _getActionMsgs_fixedQuant_extended — exec_env.py:838-932
 // + simplest_case (:935-999), fixed_quants_1msg (:732-836), twap (:1126-1227): rows = n_action_msgs
+template <class Rows>
 DEV void exe_fqc(const hftlob_env_cfg& c, const hftlob_agent_type_cfg& tc, const i32* st, i32 tid, i32 action, i32 wt0,
-                 i32 wt1, i32 last_ba, i32 last_bb, i32 step, i32 max_steps, i32* lds_rows, int row) {
+                 i32 wt1, i32 last_ba, i32 last_bb, i32 step, i32 max_steps, Rows lds_rows, int row) {
     const i32 tick = c.tick_size;
     const i32 ba = wmul(tick_floordiv(c, last_ba), tick), bb = wmul(tick_floordiv(c, last_bb), tick);
     const i32 sell = st[3];
@@ -2293,8 +2411,9 @@ DEV void exe_fqc(const hftlob_env_cfg& c, const hftlob_agent_type_cfg& tc, const
 // price levels of (FT, M, NT, PP) / (FT, NT, PP) / (FT, NT) / (FT).  Quantities are
 // rescaled in f32 to the quantity left when they sum past it; the reference prices
 // are the f32 means of the last 10 best quotes of the previous step, floored to the tick.
+template <class Rows>
 DEV void exe_fixed_prices(const hftlob_env_cfg& c, const hftlob_agent_type_cfg& tc, const i32* rec, const i32* st,
-                          i32 tid, const i32 (&act)[4], i32 wt0, i32 wt1, i32* lds_rows, int row) {
+                          i32 tid, const i32 (&act)[4], i32 wt0, i32 wt1, Rows lds_rows, int row) {
     const i32 tick = c.tick_size, w = tc.n_actions, left = wsub(st[1], st[2]), sell = st[3];
     i32 sum = 0;
     for (int j = 0; j < w; ++j) sum = wadd(sum, act[j]);
@@ -3279,10 +3398,18 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
     }
     SUBSTAMP(t_load);
 
-    // ---- (C) agent messages -> LDS rows [cancels C][actions A]
+    // ---- (C) agent messages -> rows [cancels C][actions A]: in LDS, or lane r = row r (REG)
 #ifdef HFTLOB_STAMPS
     unsigned long long acc_act = 0, acc_cnl = 0, acc_flt = 0, acc_mmr = 0, acc_exr = 0, acc_obs = 0;
 #endif
+    constexpr bool REG = NFIX > 0 && !RA;  // (C + A <= 64 there: reg_rows_ok, the launch code's rule)
+    RegRows<S> sink;  // (REG only)
+    if constexpr (REG) {
+        SUBSTAMP(tc0);
+        sink.init(B.a.t, B.b.t, R, C, wt0, wt1);
+        STAMP_ACC(acc_cnl, tc0);  // (the columns' issue; their wait falls to the first reader)
+    }
+    const auto srows = row_sink<REG>(sink, rows);  // the agent functions' row sink
     {
         int ag = 0, arow = C, crow = 0, aw = 0;
         const i32* st = rec + c.off_agents;
@@ -3332,7 +3459,7 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
 #ifndef HFTLOB_KO_CNL
                     if (k >= tc.n_action_msgs) continue;
 #endif
-                    put_row(rows, k < tc.n_action_msgs ? arow + k : crow + k - tc.n_action_msgs, 0, 0, 0, 0, 0, 0, 0, 0);
+                    put_row(srows, k < tc.n_action_msgs ? arow + k : crow + k - tc.n_action_msgs, 0, 0, 0, 0, 0, 0, 0, 0);
                 }
 #endif
 #ifdef HFTLOB_DUP_AGENT  // timing builds only: the agent's action (bit 0) / cancel (bit 1) rows computed twice
@@ -3350,18 +3477,23 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
 #ifndef HFTLOB_KO_ACT
                     if (!do_act) {
                     } else if (tc.action_space == HFTLOB_MM_ACT_DIRECTIONAL)
-                        mm_directional(c, tc, tid_r, act_r, wt0, wt1, ba_r, old_last_bb, rows, arow, x);
+                        mm_directional(c, tc, tid_r, act_r, wt0, wt1, ba_r, old_last_bb, srows, arow, x);
                     else if (tc.action_space == HFTLOB_MM_ACT_FIXED_QUANTS)
-                        mm_fixed_quant(c, tc, B, s4, tid_r, act_r, wt0, wt1, ba_r, old_last_bb, rows, arow, x);
+                        mm_fixed_quant(c, tc, B, s4, tid_r, act_r, wt0, wt1, ba_r, old_last_bb, srows, arow, x);
                     else
-                        mm_other_actions(c, tc, B, s4, tid_r, act_r, wt0, wt1, ba_r, old_last_bb, step, ld_t0, rows,
+                        mm_other_actions(c, tc, B, s4, tid_r, act_r, wt0, wt1, ba_r, old_last_bb, step, ld_t0, srows,
                                          arow, x);
 #endif
                     STAMP_ACC(acc_act, ta0);
                     SUBSTAMP(ta1);
                     const int sz = tc.n_msgs / 4;
 #ifndef HFTLOB_KO_CNL
-                    if (do_cnl) {
+                    if constexpr (REG) {
+                        if (do_cnl) {
+                            cancel_regs(sink, sink.bt, sink.bq, sink.bo, B.b.pc, B.vs, tid_r, sz, 1, crow);
+                            cancel_regs(sink, sink.at, sink.aq, sink.ao, B.a.pc, B.vs, tid_r, sz, -1, crow + sz);
+                        }
+                    } else if (do_cnl) {
                         cancel_rows(B.b, R, B.vs, tid_r, sz, 1, wt0, wt1, rows, crow);
                         cancel_rows(B.a, R, B.vs, tid_r, sz, -1, wt0, wt1, rows, crow + sz);
                     }
@@ -3371,17 +3503,23 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
 #ifndef HFTLOB_KO_ACT
                     if (!do_act) {
                     } else if (NFIX == 0 && tc.action_space == HFTLOB_EXE_ACT_FIXED_PRICES)
-                        exe_fixed_prices(c, tc, rec, s4, tid_r, av, wt0, wt1, rows, arow);
+                        exe_fixed_prices(c, tc, rec, s4, tid_r, av, wt0, wt1, srows, arow);
                     else
-                        exe_fqc(c, tc, s4, tid_r, act_r, wt0, wt1, ba_r, old_last_bb, step, max_steps, rows, arow);
+                        exe_fqc(c, tc, s4, tid_r, act_r, wt0, wt1, ba_r, old_last_bb, step, max_steps, srows, arow);
 #endif
                     STAMP_ACC(acc_act, ta0);
                     SUBSTAMP(ta1);
 #ifndef HFTLOB_KO_CNL
                     const i32 sell = s4[3];
-                    if (do_cnl)
+                    if constexpr (REG) {
+                        if (do_cnl) {  // (the task's side of the step's column registers)
+                            if (sell) cancel_regs(sink, sink.at, sink.aq, sink.ao, B.a.pc, B.vs, tid_r, tc.n_msgs / 2, -1, crow);
+                            else cancel_regs(sink, sink.bt, sink.bq, sink.bo, B.b.pc, B.vs, tid_r, tc.n_msgs / 2, 1, crow);
+                        }
+                    } else if (do_cnl) {
                         cancel_rows(sell ? B.a : B.b, R, B.vs, tid_r, tc.n_msgs / 2, wsub(1, wmul(sell, 2)), wt0, wt1,
                                     rows, crow);
+                    }
 #endif
                     STAMP_ACC(acc_cnl, ta1);
                 }
@@ -3394,11 +3532,18 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
                     for (int k = 0; k < 6; ++k) if (l == k) v = xv[k];
                     if (l < 6) axs[ag * 6 + l] = v;
                 }
+                // REG: the agent's lanes; the filter runs once below, over every agent's rows
+                // (n_action_msgs is 1, 2 or 4 there: the 100/100 kernel has no fixed_prices type, nfix_kernel)
+                if constexpr (REG)
+                    sink.agent(arow, crow, tc.n_action_msgs, tid, wadd(wt0, tc.time_delay_obs_act),
+                               wadd(wt1, tc.time_delay_obs_act));
 #ifndef HFTLOB_KO_FILTER  // timing knockout builds only (wrong results)
-                if (tc.n_action_msgs == 2) filter_rows<2>(rows, arow, crow, B.a.scr);
-                else if (tc.n_action_msgs == 4) filter_rows<4>(rows, arow, crow, B.a.scr);
-                else if (NFIX == 0 && tc.n_action_msgs == 3) filter_rows<3>(rows, arow, crow, B.a.scr);  // fixed_prices
-                else filter_rows<1>(rows, arow, crow, B.a.scr);
+                if constexpr (!REG) {
+                    if (tc.n_action_msgs == 2) filter_rows<2>(rows, arow, crow, B.a.scr);
+                    else if (tc.n_action_msgs == 4) filter_rows<4>(rows, arow, crow, B.a.scr);
+                    else if (NFIX == 0 && tc.n_action_msgs == 3) filter_rows<3>(rows, arow, crow, B.a.scr);  // fixed_prices
+                    else filter_rows<1>(rows, arow, crow, B.a.scr);
+                }
 #endif
                 STAMP_ACC(acc_flt, ta2);
                 arow += tc.n_action_msgs;
@@ -3407,10 +3552,34 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
             }
         }
     }
+#ifndef HFTLOB_KO_FILTER
+    if constexpr (REG) {
+        SUBSTAMP(tf0);
+        filter_regs(sink, C);
+        STAMP_ACC(acc_flt, tf0);
+    }
+#endif
     wave_sync();
     SUBSTAMP(t_rows);
-    // order ids (counter - j) and the action-row permutation (lane j = action row j)
-    {
+    // order ids (counter - j) and the action-row permutation
+    if constexpr (REG) {  // lane C + j = action row j: the rows move between lanes, one ds_permute a field
+        const int j = l - C;
+        const bool act_lane = (j >= 0) & (j < A);
+        if (act_lane) sink.y.x = wsub(oidc, j);
+        if (c.shuffle_action_messages && A >= 2) {
+            const u32 bits = (u32)__builtin_amdgcn_ds_bpermute((j & 63) << 2, (i32)SK.shuffle_bits);
+            int rank = 0;
+            for (int k = 0; k < A; ++k) {
+                const u32 bk = (u32)rdl((i32)SK.shuffle_bits, k);
+                rank += (bk < bits) || (bk == bits && k < j);
+            }
+            const int dest = (act_lane ? C + rank : l) << 2;  // (a permutation of the wave's lanes)
+            sink.x.x = __builtin_amdgcn_ds_permute(dest, sink.x.x); sink.x.y = __builtin_amdgcn_ds_permute(dest, sink.x.y);
+            sink.x.z = __builtin_amdgcn_ds_permute(dest, sink.x.z); sink.x.w = __builtin_amdgcn_ds_permute(dest, sink.x.w);
+            sink.y.x = __builtin_amdgcn_ds_permute(dest, sink.y.x); sink.y.y = __builtin_amdgcn_ds_permute(dest, sink.y.y);
+            sink.y.z = __builtin_amdgcn_ds_permute(dest, sink.y.z); sink.y.w = __builtin_amdgcn_ds_permute(dest, sink.y.w);
+        }
+    } else {  // (lane j = action row j)
         i32 f[8];
         const bool act_lane = l < A;
         if (act_lane) {
@@ -3446,6 +3615,9 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
     float mid_acc = 0.0f, pa_acc = 0.0f, pb_acc = 0.0f;
     i32 last_p_a = 0, last_p_b = 0, last_t0 = 0, last_t1 = 0;
     int4 nx = px, ny = py;  // the chunk's data rows, loaded one chunk ahead (chunk 0's at kernel start)
+    if constexpr (REG) {    // chunk 0's agent rows are in their lanes already
+        if (l < AR) { nx = sink.x; ny = sink.y; }
+    }
 #ifndef HFTLOB_NO_CARRY  // (A/B builds only)
     i32* carry = B.filt - PAD_FILT + PAD_CARRY;
     if (!RA && resident) {  // the previous step's quotes and caches: the book is unchanged since
@@ -3466,7 +3638,8 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
 #endif
         const int row = base + l;
         int4 x = nx, y = ny;
-        if (RA ? (base == 0) & (row < AR) : row < AR) {  // (RA: chunk 1's agent rows came with chunk 0's)
+        if (REG) {  // (the agent rows came in nx, ny)
+        } else if (RA ? (base == 0) & (row < AR) : row < AR) {  // (RA: chunk 1's agent rows came with chunk 0's)
             x = reinterpret_cast<const int4*>(rows + row * 8)[0];
             y = reinterpret_cast<const int4*>(rows + row * 8)[1];
         } else if (ftime && base > 0 && row >= AR) {
@@ -4318,11 +4491,18 @@ static bool use_rows_alias(const hftlob_env_cfg* cfg) {
            4 * lds_map(*cfg, cfg->lob.n_orders, cfg->lob.n_trades, false).words > 160 * 1024 / 16;
 }
 
+// the 100/100 kernel without the rows alias holds the step's agent rows in the lanes of message
+// chunk 0 (RegRows): at most 64 of them.  (Today more rows than that always take the alias, their
+// own region would pass the LDS share above; stated here so that no change of sizes can launch the
+// register path with rows it has no lanes for.)
+static bool reg_rows_ok(const hftlob_env_cfg* cfg) { return cfg->n_cancel_msgs + cfg->n_action_msgs <= 64; }
+
 // The kernel variant a (checked) config launches, one of HFTLOB_VARIANTS: the rule every env launch
 // and hftlob_env_launch_info share.  cancel_mode 2 / 3 takes the random-cancel kernels (general
 // sizes only), else 100/100 configs the 100/100 kernel (it has no MultiDiscrete / fixed_prices
-// path: nfix_kernel), with the rows-in-trades layout where that pays; the others the general-size
-// kernel of their slot sets.  kb: the config derives its rollout step keys in batches (the sampled
+// path: nfix_kernel), with the rows-in-trades layout where that pays and, without it, only up to
+// 64 agent rows (reg_rows_ok); the others the general-size kernel of their slot sets.
+// kb: the config derives its rollout step keys in batches (the sampled
 // rollout's KB instantiations at (2, 100, false, false); decided in the kernel elsewhere).
 struct Variant {
     int S, nfix;
@@ -4331,9 +4511,9 @@ struct Variant {
 static Variant env_variant(const hftlob_env_cfg* cfg) {
     Variant v;
     v.rc = cfg->lob.cancel_mode >= 2;
-    v.nfix = nfix_kernel(cfg) ? 100 : 0;
-    v.S = v.nfix ? 2 : slot_sets(cfg->lob.n_orders > cfg->lob.n_trades ? cfg->lob.n_orders : cfg->lob.n_trades);
     v.ra = use_rows_alias(cfg);
+    v.nfix = nfix_kernel(cfg) && (v.ra || reg_rows_ok(cfg)) ? 100 : 0;
+    v.S = v.nfix ? 2 : slot_sets(cfg->lob.n_orders > cfg->lob.n_trades ? cfg->lob.n_orders : cfg->lob.n_trades);
     v.kb = kb_ok(*cfg);
     return v;
 }
