@@ -24,6 +24,9 @@
  *                           reset_env :129-207 (vmapped over envs).
  *   hftlob_env_step      <- jaxen/marl_env.py:775-804 MARLEnv.step (step_env
  *                           :211-709 + auto-reset select), vmapped over envs.
+ *   hftlob_env_rollout_eval <- jaxrl/MARL/baseline_eval/baseline_only_JAXMARL.py: the scanned
+ *                           _env_step with FixedAction policies and the reduction of its
+ *                           trajectory batch (avg_reward, total_dones, info means / stds).
  *   hftlob_sample_actions<- jaxen/Speed_test.py:166-177 (per-env random actions
  *                           via gymnax Discrete.sample = jax.random.randint).
  *   hftlob_split_keys    <- jax.random.split(key, n) (threefry2x32), batched.
@@ -369,6 +372,40 @@ int hftlob_env_rollout_actions(const hftlob_env_cfg* cfg /*[host]*/, int n_env, 
                                int32_t* state, const hftlob_step_out* out /*[host] struct*/, int per_step,
                                void* stream);
 
+/* Evaluation rollout — replaces the reset / step / reduce loop of
+ * gymnax_exchange/jaxrl/MARL/baseline_eval/baseline_only_JAXMARL.py (make_eval: _env_step scanned
+ * NUM_STEPS times, then the trajectory batch reduced to means and standard deviations): n_steps
+ * MARLEnv.step calls in ONE persistent launch as hftlob_env_rollout_actions with per_step == 0
+ * makes them, whose every step also folds the agents' rewards and info words into `stats`.
+ * keys uint32 [n_steps][n_env][2]; actions int32 [n_steps][n_env][action_words], or with
+ * actions_fixed != 0 ONE row [action_words] read for every env and step (the script's FixedAction).
+ * The state after the call and `out` (the last step's outputs) are bit for bit those of
+ * hftlob_env_rollout_actions with per_step == 0 over the same keys and the expanded actions; the
+ * steps before the last build no observation and store no output.  n_env and n_steps must be >= 1.
+ * stats double [n_env][n_agents][HFTLOB_EVAL_WORDS], in/out: the call ADDS to what it finds, so a
+ * long evaluation can be cut into calls (zero it before the first).  Quantity q of an agent at a
+ * step: q = 0 its reward as stored to `rewards`, q = 1 + k its info word k
+ * (HFTLOB_INFO_AGENT_WORDS of them, taken before the auto-reset as `info` is; words the agent's
+ * kind does not use are 0), each widened exactly: float words float -> double, int words int32 ->
+ * double (the map per kind is INFO_MM / INFO_EXE of hftlob/layout.py).  Words of an agent's row:
+ *   0              steps tallied
+ *   1              episodes completed (steps whose done_all was set)
+ *   2, 3           the running episode's reward sum and length (both 0 again after an episode end)
+ *   4, 5           sum and sum of squares of the completed episodes' reward sums
+ *   6, 7           sum and sum of squares of the completed episodes' lengths
+ *   8+2q, 9+2q     (q = 0..24) sum and sum of squares of quantity q over all tallied steps
+ *   58+2k, 59+2k   (k = 0..23) sum and sum of squares of info word k at each episode's last step
+ * Every word is a plain sequential double sum in step order (no fused multiply-add; the square of a
+ * widened float or int32 is exact), so a sequential float64 loop over per-step outputs gives the
+ * same bits (hftlob/evaluate.py reduce_steps).  The kernel instantiation follows the rule of the
+ * other env launches (hftlob_env_launch_info, apart from key_batch); the call neither allocates
+ * nor synchronises and can be captured in a hipGraph. */
+#define HFTLOB_EVAL_WORDS 106
+int hftlob_env_rollout_eval(const hftlob_env_cfg* cfg /*[host]*/, int n_env, int n_steps, const uint32_t* keys,
+                            const int32_t* actions, int actions_fixed, const int32_t* msg_data,
+                            const int32_t* init_states, int32_t* state, double* stats,
+                            const hftlob_step_out* out /*[host] struct*/, void* stream);
+
 /* Creates the library streams / events hftlob_env_rollout_sampled needs for n_slices
  * slices on the device of `stream` (host-only; idempotent). */
 int hftlob_rollout_prepare(int n_slices, void* stream);
@@ -381,7 +418,8 @@ int hftlob_rollout_prepare(int n_slices, void* stream);
 int hftlob_env_lds_bytes(const hftlob_env_cfg* cfg /*[host]*/);
 
 /* Which kernel instantiation hftlob_env_step / hftlob_env_rollout_sampled /
- * hftlob_env_rollout_actions launch for this config (key_batch: the sampled rollout only), and
+ * hftlob_env_rollout_actions / hftlob_env_rollout_eval launch for this config (key_batch: the
+ * sampled rollout only), and
  * the launch-derived constants they pass it (host-only, no device call).  Tests use it to assert which code path a parity case ran; it replaces nothing in the reference.
  *   slot_sets     register sets per lane (1, 2 or 4: n_orders / n_trades up to 64 / 128 / 256)
  *   nfix          100: the 100/100-slot specialisation; 0: the general-size kernel

@@ -3280,14 +3280,74 @@ __global__ __launch_bounds__(64) void k_book_process_depth(hftlob_lob_cfg cfg, i
 // ====================================================== K2: fused env step
 // MARLEnv.step — marl_env.py:775-804 (step_env :211-709, auto-reset select)
 #define MAX_AGENT_ROWS 128
+
+// The tally step's accumulators (k_env_rollout_eval; the words table is in hftlob.h): an agent's
+// HFTLOB_EVAL_WORDS doubles in HBM, read, added to and written back by the env's own wave, a word
+// per lane and accumulator, so each word is one sequential double sum in step order.  The lanes:
+//   0..24   quantity q = lane (0 the reward, 1 + k info word k): words 8 + 2q (sum), 9 + 2q (squares)
+//   32..39  header word lane - 32; the lanes that need the running episode's reward sum (word 2:
+//           lanes 34, 36, 37) or its length (word 3: 35, 38, 39) load that word as well
+//   40..63  info word k = lane - 40 at an episode's last step: words 58 + 2k, 59 + 2k
+// tally_load issues the loads before the agent's reward is computed and tally_store consumes them
+// after it, so their latency (HBM, or L2 after the launch's first step) lies under the reward's.
+// The float words of the agents' info blocks (hftlob/layout.py INFO_MM / INFO_EXE), as bit masks:
+constexpr u32 INFO_F32_MM = 0xC0B9FFu, INFO_F32_EXE = 0x13Cu;
+constexpr u32 TALLY_SUM_LANES = 0x34u;  // header lanes (bit lane - 32) whose second word is the running sum
+struct TallyLane { double a, b; };
+DEV int tally_word(int l) { return l < 25 ? 8 + 2 * l : (l < 40 ? l - 32 : 58 + 2 * (l - 40)); }
+DEV TallyLane tally_load(const double* row, bool all) {
+    const int l = lane_id();
+    const bool hdr = (l >= 32) & (l < 40);
+    TallyLane t{0.0, 0.0};
+    if ((l < 25) | hdr | ((l >= 40) & all)) {
+        const int w = tally_word(l);
+        t.a = row[w];
+        t.b = row[hdr ? (((TALLY_SUM_LANES >> (l - 32)) & 1u) ? 2 : 3) : w + 1];
+    }
+    return t;
+}
+// rew / iw: the agent's reward as stored to `rewards` and its info words (wave-uniform); f32: the
+// kind's float words.  Every value is widened exactly (float or int32 -> double), so its square is
+// exact as well.
+DEV void tally_store(double* row, const TallyLane& t, float rew, const i32 (&iw)[HFTLOB_INFO_AGENT_WORDS], u32 f32,
+                     bool all) {
+    const int l = lane_id();
+    const int k = l < 25 ? l - 1 : l - 40;  // the quantity lanes' info word (lane 0: the reward)
+    i32 v = 0;
+#pragma unroll
+    for (int j = 0; j < HFTLOB_INFO_AGENT_WORDS; ++j) v = k == j ? iw[j] : v;
+    double x = ((f32 >> (k & 31)) & 1u) ? (double)bitf(v) : (double)v;
+    if (l == 0) x = (double)rew;
+    if ((l >= 32) & (l < 40)) {
+        const int h = l - 32;
+        // the running episode's reward sum / length with this step
+        const double run = t.b + (((TALLY_SUM_LANES >> h) & 1u) ? (double)rew : 1.0);
+        double a;
+        if (h == 0) a = t.a + 1.0;                          // steps tallied
+        else if (h == 1) a = t.a + (all ? 1.0 : 0.0);       // episodes completed
+        else if (h < 4) a = all ? 0.0 : run;                // running sum / length
+        else if ((h & 1) == 0) a = all ? t.a + run : t.a;   // completed episodes: sums
+        else a = all ? t.a + run * run : t.a;               // and their squares
+        row[h] = a;
+    } else if ((l < 25) | ((l >= 40) & all)) {
+        const int w = tally_word(l);
+        row[w] = t.a + x;
+        row[w + 1] = t.b + x * x;
+    }
+}
 // NFIX > 0: nOrders == nTrades == NFIX known at compile time (the reference's
 // 100/100 default), which folds the slot-validity masks away.
-template <int S, int NFIX, bool RC, bool RA = false, bool QUIET = false, int PK = -1>
+template <int S, int NFIX, bool RC, bool RA = false, bool QUIET = false, int PK = -1, bool TALLY = false>
 // RC: cancel_mode 2/3 (the random cancel fallback of the engine).  RA: the agent rows live in the
 // trade log (lds_map).  QUIET: a step whose outputs are never emitted (emit = false at compile
 // time: k_env_rollout's per_step = 0 steps before the last, whose copy of the step body then holds
 // no observation or reward-value code).  PK: 1 = the step's keys always come from a key-batch row
 // (pre_keys, k_env_rollout's KB = 1), 0 = never, -1 = as pre_keys is given.
+// TALLY: the tally step of k_env_rollout_eval: the reward values, the dones and the agents' info
+// words are computed on every step, an episode's last included, and folded into the env's rows of
+// `stats` (tally_load / tally_store); with QUIET nothing else of them leaves the wave (no
+// observation, no output store), without QUIET the step emits as well (the launch's last step).
+// act_e: the env index of this step's actions row (-1: e; 0: one row for every env).
 // master: Speed_test rollout mode — the env's step key is split(mk, n_env + 1)[e + 1],
 // actions are sampled here (hftlob_sample_actions) and written to actions_io if it is not
 // NULL; mk becomes split(mk)[0].  Otherwise keys / actions_io are the inputs.  (mk is a
@@ -3307,8 +3367,10 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
                       float* __restrict__ rew_out, u8* __restrict__ done_all_out, u8* __restrict__ dones_out,
                       i32* __restrict__ info_out, i32* __restrict__ obs_raw_out, i32* __restrict__ msgs_out,
                       i32* __restrict__ debug_out, i32* lds, bool resident, bool keep, u32& fl_carry,
-                      const i32* pre_keys = nullptr, bool emit_rt = true) {
+                      const i32* pre_keys = nullptr, bool emit_rt = true, double* __restrict__ stats = nullptr,
+                      int act_e = -1) {
     const bool emit = !QUIET && emit_rt;
+    const bool vals = TALLY || emit;  // the reward values are wanted (the observations: emit)
     STAMP(t_start);
 #ifdef HFTLOB_STAMPS
     const unsigned long long rt_start = __builtin_amdgcn_s_memrealtime();  // 100 MHz: the in-kernel clock
@@ -3358,7 +3420,7 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
     for (int t = 0; t < c.n_types; ++t) {
         const bool ex = c.types[t].kind == HFTLOB_AGENT_MM && c.types[t].exclude_extreme_spreads;
         excl_cfg |= ex;
-        if (emit && ex) {
+        if (vals && ex) {
             bool any = false;
             for (int m = l; m < M; m += 64) {
                 const i32 pa = rec[c.off_best_asks + m * 2], pb = rec[c.off_best_bids + m * 2];
@@ -3418,7 +3480,7 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
             for (int i = 0; i < tc.n_agents; ++i, ++ag) {
                 const i32 tid = wsub(tc.trader_id0, i);
                 const int w = tc.action_width;
-                i32* aio = actions_io ? actions_io + (size_t)e * c.action_words + aw : nullptr;
+                i32* aio = actions_io ? actions_io + (size_t)(act_e < 0 ? e : act_e) * c.action_words + aw : nullptr;
                 aw += w;
                 i32 act, av[4] = {0, 0, 0, 0};
                 if (NFIX > 0 || w == 1) {  // the 100/100 kernel is launched for Discrete spaces only
@@ -3749,7 +3811,7 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
     const float dt = i2f(last_t0) + i2f(last_t1) / 1e9f - i2f(wt0) - i2f(wt1) / 1e9f;  // marl_env.py:496
     wv.dt = dt;
     i32* info = info_out ? info_out + (size_t)e * c.info_words : nullptr;
-    if (emit | !all) {  // (an unemitted episode end: the auto-reset below replaces every agent state)
+    if (vals | !all) {  // (an episode end whose values nobody reads: the auto-reset below replaces every agent state)
         // the step's trade log as the rewards read it, loaded once for every agent
         TradeView<S> TV;
         {
@@ -3770,6 +3832,10 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
                 }
                 i32 d = 0;
                 float rew;
+                TallyLane tl{0.0, 0.0};  // (TALLY: the lane's accumulators, on their way while the reward is computed)
+#ifndef HFTLOB_KO_TALLY  // timing knockout builds only (no statistics)
+                if constexpr (TALLY) tl = tally_load(stats + ((size_t)e * c.n_agents + ag) * HFTLOB_EVAL_WORDS, all);
+#endif
                 i32 iw[HFTLOB_INFO_AGENT_WORDS];
                 for (int k = 0; k < HFTLOB_INFO_AGENT_WORDS; ++k) iw[k] = 0;
                 ActX ax1;
@@ -3782,7 +3848,7 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
 #if defined(HFTLOB_KO_REWARD) || defined(HFTLOB_KO_MM_REWARD)  // timing knockout builds only (wrong results)
                     memset(&R, 0, sizeof R);
 #else
-                    mm_reward(c, tc, B, X, s, tid, excl_any, TV, R, emit);
+                    mm_reward(c, tc, B, X, s, tid, excl_any, TV, R, vals);
 #endif
                     STAMP_ACC(acc_mmr, tr0);
                     const float tot = bitf(s[3]) + R.PnL;
@@ -3803,7 +3869,7 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
 #if defined(HFTLOB_KO_REWARD) || defined(HFTLOB_KO_EXE_REWARD)
                     memset(&R, 0, sizeof R);
 #else
-                    exe_reward(c, tc, B, X, s, tid, TV, R, emit);
+                    exe_reward(c, tc, B, X, s, tid, TV, R, vals);
 #endif
                     STAMP_ACC(acc_exr, tr0);
                     s[2] = wadd(s[2], R.agentQuant);
@@ -3819,6 +3885,11 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
                     iw[4] = fbit(R.drift); iw[5] = fbit(R.advantage); iw[6] = R.doom_quant; iw[7] = s[3];
                     iw[8] = fbit(R.reward_info);
                 }
+#ifndef HFTLOB_KO_TALLY
+                if constexpr (TALLY)
+                    tally_store(stats + ((size_t)e * c.n_agents + ag) * HFTLOB_EVAL_WORDS, tl, rew, iw,
+                                tc.kind == HFTLOB_AGENT_MM ? INFO_F32_MM : INFO_F32_EXE, all);
+#endif
                 if (emit & (l == 0)) {
                     rew_out[(size_t)e * c.n_agents + ag] = rew;
                     dones_out[(size_t)e * c.n_agents + ag] = (u8)(d != 0);
@@ -4178,6 +4249,69 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout_actions(hftlob_env_cfg c,
 #endif
 }
 
+// Fixed-action / scripted evaluation (hftlob_env_rollout_eval): k_env_rollout_actions' launch with
+// the tally step in place of the quiet one.  Steps 0 .. n_steps - 2 compute the reward values and
+// info words and fold them into the env's rows of `stats` (double [n_env][n_agents]
+// [HFTLOB_EVAL_WORDS], in/out) without an observation or an output store; the last step emits to
+// `out` as per_step = 0 does and is tallied as well.  The state and `out` are bit for bit those of
+// k_env_rollout_actions with per_step = 0.  fixed: `actions` is one row [action_words], read for
+// every env and step.
+template <int S, int NFIX, bool RC, bool RA = false>
+__global__ __launch_bounds__(64, 4) void k_env_rollout_eval(hftlob_env_cfg c, int n_env, int n_steps, int fixed,
+                                                         const u32* __restrict__ keys,
+                                                         const i32* __restrict__ actions,
+                                                         const i32* __restrict__ msg_data,
+                                                         const i32* __restrict__ init_states,
+                                                         i32* __restrict__ state, double* __restrict__ stats,
+                                                         hftlob_step_out out) {
+    one_wave();
+    extern __shared__ __attribute__((aligned(16))) i32 lds[];
+    const int e = blockIdx.x;
+    if (e >= n_env) return;
+    Key mk{0u, 0u};  // (env_step_dev's master-key reference: never read with master = false)
+    kcfg_t* kp = (kcfg_t*)__builtin_amdgcn_kernarg_segment_ptr();
+    bool resident = false;  // (the 100/100 instantiation only, as in k_env_rollout)
+    u32 fl = 0;
+#ifndef HFTLOB_NO_BALANCE
+    const unsigned long long bal_r0 = __builtin_amdgcn_s_memrealtime();
+    const u32 bal_hwid = __builtin_amdgcn_s_getreg(0xF804), bal_xcc = __builtin_amdgcn_s_getreg(0x7814);
+    u32 bal_slot;
+    unsigned long long* bal_row = wave_row(bal_hwid, bal_xcc, bal_slot);
+#endif
+    // one step: Q = true for a tally step that emits nothing (every step but the last); the per-step
+    // opaque copies keep the body's invariants out of the step loop's preheader (see k_env_rollout)
+    auto step = [&](auto Q, int t) {
+        constexpr bool QT = decltype(Q)::value;
+        kcfg_t* cp = kp;
+        i32* st = state;
+        const i32* md = msg_data;
+        const i32* is = init_states;
+        double* sp = stats;
+        asm volatile("" : "+s"(cp), "+s"(st), "+s"(md), "+s"(is), "+s"(sp));
+        const hftlob_env_cfg& cc = *(const hftlob_env_cfg*)cp;
+        const bool ox = !QT;  // (the optional outputs: written by the emitted step only)
+        const bool reset = env_step_dev<S, NFIX, RC, RA, QT, /*PK=*/0, /*TALLY=*/true>(
+            cc, n_env, e, e, keys + (size_t)t * n_env * 2, false, mk,
+            const_cast<i32*>(actions) + (fixed ? (size_t)0 : (size_t)t * n_env * cc.action_words), md, is, st, out.obs,
+            out.rewards, out.done_all, out.dones, ox ? out.info : nullptr, ox ? out.obs_raw : nullptr,
+            ox ? out.msgs : nullptr, ox ? out.debug : nullptr, lds, NFIX > 0 && resident, NFIX > 0 && t + 1 < n_steps, fl,
+            nullptr, !QT, sp, fixed ? 0 : -1);
+        resident = uni(!reset) != 0;  // (an auto-reset rewrote the record: the next step loads the book from it)
+#ifndef HFTLOB_NO_BALANCE
+        if ((t + 1 < n_steps) && ((t % HFTLOB_BALANCE_EVERY) == 0) && (n_env > HFTLOB_BALANCE_MIN_ENVS))
+            balance_prio(bal_row, bal_slot, bal_r0, t + 1, n_steps - t - 1);
+#endif
+    };
+    int t = 0;
+#pragma unroll 1
+    for (; t + 1 < n_steps; ++t) step(std::integral_constant<bool, true>{}, t);
+    step(std::integral_constant<bool, false>{}, t);
+#ifndef HFTLOB_NO_BALANCE
+    if (lane_id() == 0) __hip_atomic_store(bal_row + bal_slot, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
+                                           HFTLOB_PRIO_SCOPE);
+#endif
+}
+
 // ==================================================== K3/K4: PRNG kernels
 #if !defined(HFTLOB_INST)  // (non-template kernels: the main translation unit only)
 __global__ void k_sample_actions(hftlob_env_cfg c, int n_env, const u32* __restrict__ keys, i32* __restrict__ actions) {
@@ -4210,7 +4344,7 @@ __global__ void k_split_keys(int n_env, int n, int part, const u32* __restrict__
 #endif  // !HFTLOB_INST
 
 // ============================================ kernel variants (parallel build)
-// The env kernels (k_env_step, k_env_rollout, k_env_rollout_actions) exist in these
+// The env kernels (k_env_step, k_env_rollout, k_env_rollout_actions, k_env_rollout_eval) exist in these
 // (S, NFIX, RC, RA) variants and no others: the general-size kernels at 1 / 2 / 4 slot sets without
 // and with the random cancel, and the 100/100 kernel without and with the rows-in-trades layout.
 // env_variant (below) picks one for a config; the declarations and the dispatch come from this list.
@@ -4233,6 +4367,8 @@ constexpr bool is_variant(int S, int NFIX, bool RC, bool RA) {
 #define HFTLOB_ROLL_ARGS hftlob_env_cfg, int, int, int, int, int, const u32*, u32*, i32*, const i32*, const i32*, i32*, \
                          hftlob_step_out
 #define HFTLOB_RACT_ARGS hftlob_env_cfg, int, int, int, const u32*, const i32*, const i32*, const i32*, i32*, hftlob_step_out
+#define HFTLOB_REVAL_ARGS hftlob_env_cfg, int, int, int, const u32*, const i32*, const i32*, const i32*, i32*, double*, \
+                          hftlob_step_out
 #define HFTLOB_LISTED(SS, NF, RC, RA) static_assert(is_variant(SS, NF, RC, RA), "not in HFTLOB_VARIANTS");
 #define HFTLOB_STEP(P, SS, NF, RC, RA) \
     HFTLOB_LISTED(SS, NF, RC, RA) P template __global__ void k_env_step<SS, NF, RC, RA>(HFTLOB_STEP_ARGS);
@@ -4242,12 +4378,14 @@ constexpr bool is_variant(int S, int NFIX, bool RC, bool RA) {
     HFTLOB_LISTED(2, 100, false, false) P template __global__ void k_env_rollout<2, 100, false, false, KB>(HFTLOB_ROLL_ARGS);
 #define HFTLOB_RACT(P, SS, NF, RC, RA) \
     HFTLOB_LISTED(SS, NF, RC, RA) P template __global__ void k_env_rollout_actions<SS, NF, RC, RA>(HFTLOB_RACT_ARGS);
+#define HFTLOB_REVAL(P, SS, NF, RC, RA) \
+    HFTLOB_LISTED(SS, NF, RC, RA) P template __global__ void k_env_rollout_eval<SS, NF, RC, RA>(HFTLOB_REVAL_ARGS);
 // The Makefile compiles this file HFTLOB_NPARTS + 1 times: part k (HFTLOB_INST = k) instantiates the
 // kernels HFTLOB_PARTk names, the main translation unit (no HFTLOB_INST) declares every listed
 // variant's kernels extern and holds the small kernels and the C ABI.  Which part a kernel builds
 // in only balances the parallel build (part 1 stays the metric kernel alone: `make asm`); a listed
 // kernel that no part instantiates fails the link (-z defs).
-#define HFTLOB_NPARTS 13
+#define HFTLOB_NPARTS 17
 #define HFTLOB_PART1(P) HFTLOB_ROLL_KB(P, 1)
 #define HFTLOB_PART2(P) HFTLOB_STEP(P, 2, 100, false, false)
 #define HFTLOB_PART3(P) HFTLOB_ROLL(P, 1, 0, false, false) HFTLOB_STEP(P, 1, 0, false, false)
@@ -4261,6 +4399,10 @@ constexpr bool is_variant(int S, int NFIX, bool RC, bool RA) {
 #define HFTLOB_PART11(P) HFTLOB_RACT(P, 2, 100, false, true) HFTLOB_RACT(P, 1, 0, true, false)
 #define HFTLOB_PART12(P) HFTLOB_RACT(P, 2, 0, false, false) HFTLOB_RACT(P, 2, 0, true, false)
 #define HFTLOB_PART13(P) HFTLOB_RACT(P, 4, 0, false, false) HFTLOB_RACT(P, 4, 0, true, false)
+#define HFTLOB_PART14(P) HFTLOB_REVAL(P, 2, 100, false, false) HFTLOB_REVAL(P, 1, 0, false, false)
+#define HFTLOB_PART15(P) HFTLOB_REVAL(P, 2, 100, false, true) HFTLOB_REVAL(P, 1, 0, true, false)
+#define HFTLOB_PART16(P) HFTLOB_REVAL(P, 2, 0, false, false) HFTLOB_REVAL(P, 2, 0, true, false)
+#define HFTLOB_PART17(P) HFTLOB_REVAL(P, 4, 0, false, false) HFTLOB_REVAL(P, 4, 0, true, false)
 #define HFTLOB_CAT_(A, B) A##B
 #define HFTLOB_CAT(A, B) HFTLOB_CAT_(A, B)
 #if defined(HFTLOB_INST)
@@ -4270,8 +4412,9 @@ constexpr bool is_variant(int S, int NFIX, bool RC, bool RA) {
 HFTLOB_CAT(HFTLOB_PART, HFTLOB_INST)()
 #else  // the main translation unit
 #if !defined(HFTLOB_SINGLE_TU)
-#define HFTLOB_X(SS, NF, RC, RA) \
-    HFTLOB_STEP(extern, SS, NF, RC, RA) HFTLOB_ROLL(extern, SS, NF, RC, RA) HFTLOB_RACT(extern, SS, NF, RC, RA)
+#define HFTLOB_X(SS, NF, RC, RA)                                                                                   \
+    HFTLOB_STEP(extern, SS, NF, RC, RA) HFTLOB_ROLL(extern, SS, NF, RC, RA) HFTLOB_RACT(extern, SS, NF, RC, RA) \
+    HFTLOB_REVAL(extern, SS, NF, RC, RA)
 HFTLOB_VARIANTS(HFTLOB_X)
 #undef HFTLOB_X
 HFTLOB_ROLL_KB(extern, 1) HFTLOB_ROLL_KB(extern, 0)
@@ -4766,6 +4909,24 @@ int hftlob_env_rollout_actions(const hftlob_env_cfg* cfg, int n_env, int n_steps
             return k_env_rollout_actions<decltype(V)::S, decltype(V)::NFIX, decltype(V)::RC, decltype(V)::RA>;
         },
         n_steps, per_step, keys, actions, msg_data, init_states, state, *out);
+}
+
+int hftlob_env_rollout_eval(const hftlob_env_cfg* cfg, int n_env, int n_steps, const uint32_t* keys,
+                            const int32_t* actions, int actions_fixed, const int32_t* msg_data,
+                            const int32_t* init_states, int32_t* state, double* stats, const hftlob_step_out* out,
+                            void* stream) {
+    int rc = check_env(cfg);
+    if (rc) return rc;
+    // (the last step always emits and every step adds to stats: no empty call, unlike the rollouts above)
+    if (n_env < 1 || n_steps < 1) return fail(HFTLOB_ESHAPE, "n_env and n_steps must be >= 1");
+    if (!keys || !actions || !msg_data || !init_states || !state || !stats || !out) return fail(HFTLOB_ENULL, "null array");
+    if (!out->obs || !out->rewards || !out->done_all || !out->dones) return fail(HFTLOB_ENULL, "null output");
+    return env_launch(
+        cfg, n_env, stream,
+        [](auto V, const Variant&) {
+            return k_env_rollout_eval<decltype(V)::S, decltype(V)::NFIX, decltype(V)::RC, decltype(V)::RA>;
+        },
+        n_steps, actions_fixed != 0 ? 1 : 0, keys, actions, msg_data, init_states, state, stats, *out);
 }
 
 int hftlob_sample_actions(const hftlob_env_cfg* cfg, int n_env, const uint32_t* keys, int32_t* actions, void* stream) {

@@ -20,10 +20,11 @@ class LaunchInfo(C.Structure):
 
 LIB_PATH = os.environ.get("HFTLOB_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhftlob.so")
 ABI_VERSION = 8
+EVAL_WORDS = 106  # HFTLOB_EVAL_WORDS: doubles per agent in hftlob_env_rollout_eval's stats (the table is in hftlob.h)
 EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob_book_depth",
            "hftlob_book_process_depth", "hftlob_env_reset",
            "hftlob_env_step", "hftlob_env_step_sampled", "hftlob_env_rollout_sampled", "hftlob_rollout_prepare",
-           "hftlob_env_rollout_actions",
+           "hftlob_env_rollout_actions", "hftlob_env_rollout_eval",
            "hftlob_env_lds_bytes", "hftlob_env_launch_info",
            "hftlob_sample_actions", "hftlob_split_keys")
 
@@ -63,6 +64,8 @@ def lib() -> C.CDLL:
     L.hftlob_env_rollout_sampled.restype = i32
     L.hftlob_env_rollout_actions.argtypes = [C.POINTER(EnvCfg), i32, i32, vp, vp, vp, vp, vp, C.POINTER(StepOut), i32, vp]
     L.hftlob_env_rollout_actions.restype = i32
+    L.hftlob_env_rollout_eval.argtypes = [C.POINTER(EnvCfg), i32, i32, vp, vp, i32, vp, vp, vp, vp, C.POINTER(StepOut), vp]
+    L.hftlob_env_rollout_eval.restype = i32
     L.hftlob_rollout_prepare.argtypes = [i32, vp]
     L.hftlob_rollout_prepare.restype = i32
     L.hftlob_env_lds_bytes.argtypes = [C.POINTER(EnvCfg)]

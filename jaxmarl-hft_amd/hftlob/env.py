@@ -605,6 +605,57 @@ class MARLEnv:
             return self._results(o, state, E)
         return self._results_steps(o, state, T, E)
 
+    def _actions_fixed(self, actions) -> torch.Tensor:
+        """rollout_eval's fixed actions -> the int32 [action_words] row of the C ABI: one such tensor,
+        or the per-type list of step without its E axis ([n_t] Discrete, [n_t, width] MultiDiscrete)."""
+        if isinstance(actions, torch.Tensor):
+            parts, shapes = [actions], [(self.action_words,)]
+        else:
+            parts = [torch.as_tensor(x) for x in actions]
+            shapes = [(n,) if isinstance(sp, Discrete) else (n, wd)
+                      for n, wd, sp in zip(self.multi_agent_config.number_of_agents_per_type, self.action_widths,
+                                           self.action_spaces)]
+            if len(parts) != len(shapes):
+                raise ValueError(f"actions must hold one tensor per agent type ({len(shapes)}), got {len(parts)}")
+        for x, shape in zip(parts, shapes):
+            if tuple(x.shape) != shape or x.dtype != torch.int32:
+                raise ValueError(f"fixed actions must be int32 {list(shape)}, got {x.dtype} {list(x.shape)}")
+        return torch.cat([x.to(self.device).reshape(-1) for x in parts]).contiguous()
+
+    def rollout_eval(self, key: torch.Tensor, state: MultiAgentState, actions, params: MultiAgentParams,
+                     stats: Optional[torch.Tensor] = None, fixed: bool = False):
+        """:meth:`rollout` with ``per_step=False`` whose every step also folds the agents' rewards
+        and info words into ``stats`` (hftlob_env_rollout_eval; the words of a row are listed in
+        include/hftlob.h and named by :class:`hftlob.evaluate.EvalStats`): the evaluation loop of the
+        reference's baseline_eval/baseline_only_JAXMARL.py in one persistent launch that builds no
+        observation and stores no per-step output.  Returns ``(obs, state, rewards, dones, info,
+        stats)``: the first five are the last step's, bit for bit what ``rollout`` gives.
+        key: uint32 / int32 [T, E, 2].  actions: as :meth:`rollout` takes them, or with
+        ``fixed=True`` ONE action row used for every env and step: int32 [action_words], or the
+        per-type list without the T and E axes.  stats: float64 [E, num_agents, EVAL_WORDS] on this
+        env's device, added to in place (so an evaluation can be cut into calls); None allocates a
+        zeroed one."""
+        if key.dtype not in (torch.int32, torch.uint32) or key.dim() != 3 or key.shape[2] != 2:
+            raise ValueError("key must be a uint32/int32 tensor [T, E, 2] (one threefry key per step and env)")
+        T, E = int(key.shape[0]), int(key.shape[1])
+        if T < 1 or E < 1:
+            raise ValueError("rollout_eval needs T >= 1 steps of E >= 1 envs")
+        if state.buf.shape[0] != E:
+            raise ValueError(f"key is for {E} envs, the state holds {state.buf.shape[0]}")
+        acts = self._actions_fixed(actions) if fixed else self._actions_steps(actions, T, E)
+        shape = (E, self.num_agents, _lib.EVAL_WORDS)
+        if stats is None:
+            stats = torch.zeros(shape, dtype=torch.float64, device=self.device)
+        elif (not isinstance(stats, torch.Tensor) or stats.dtype != torch.float64 or tuple(stats.shape) != shape
+              or stats.device != state.buf.device or not stats.is_contiguous()):
+            raise ValueError(f"stats must be a contiguous float64 {list(shape)} tensor on {state.buf.device}")
+        keys = key.to(self.device).contiguous()
+        o = self._outputs(E)
+        self._abi("hftlob_env_rollout_eval", C.byref(self.cfg_c), E, T, _lib.ptr(keys), _lib.ptr(acts), int(fixed),
+                  _lib.ptr(params.loaded_params.message_data), _lib.ptr(params.loaded_params.init_states_array),
+                  _lib.ptr(state.buf), _lib.ptr(stats), C.byref(o["struct"]))
+        return self._results(o, state, E) + (stats,)
+
     def _results_steps(self, o, state, T: int, E: int):
         """_results of per-step buffers [T, E, ...]: a leading [T] on obs / rewards / dones."""
         flat = {k: (v.reshape((T * E,) + tuple(v.shape[2:])) if isinstance(v, torch.Tensor) else v)

@@ -1,0 +1,261 @@
+"""Fixed-action baseline evaluation: the reference's
+gymnax_exchange/jaxrl/MARL/baseline_eval/baseline_only_JAXMARL.py (reset NUM_ENVS envs, step them
+NUM_STEPS times with one FixedAction per agent type, report the trajectory batch as a few numbers)
+on :meth:`MARLEnv.rollout_eval`, whose persistent launch folds every step's rewards and info words
+into per-agent accumulators instead of writing a trajectory.
+
+* :func:`reduce_steps` is the accumulators' definition, a sequential float64 loop over per-step
+  outputs in torch: what the kernel is held to (bit for bit), and the way in for someone who
+  already holds per-step outputs.
+* :class:`EvalStats` names the accumulator words (include/hftlob.h lists them) and turns them
+  into counts, means and population standard deviations per agent type.
+* :func:`evaluate_fixed_actions` is the script's loop; ``python -m hftlob.evaluate`` prints its
+  numbers as one JSON object.
+
+Checkpoint evaluation and plotting (the rest of baseline_eval/) are not covered.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import sys
+from typing import Dict, List, Optional, Sequence
+
+import torch
+
+from ._lib import EVAL_WORDS
+from .layout import AGENT_MM, INFO_AGENT_WORDS, INFO_EXE, INFO_MM, INFO_WORLD_WORDS
+
+# words of an agent's row (include/hftlob.h, hftlob_env_rollout_eval)
+W_STEPS, W_EPISODES, W_RUN_SUM, W_RUN_LEN, W_EP_SUM, W_EP_SUM2, W_EP_LEN, W_EP_LEN2 = range(8)
+W_STEP_Q = 8            # + 2q, + 2q + 1: quantity q (0 the reward, 1 + k info word k) over all steps
+W_END_INFO = 58         # + 2k, + 2k + 1: info word k at each episode's last step
+N_QUANT = 1 + INFO_AGENT_WORDS
+assert W_STEP_Q + 2 * N_QUANT == W_END_INFO and W_END_INFO + 2 * INFO_AGENT_WORDS == EVAL_WORDS
+
+
+def _float_words(layout) -> torch.Tensor:
+    """bool [n_agents, INFO_AGENT_WORDS]: the float32 words of each agent's info block."""
+    rows = []
+    for kind in layout.agent_kinds:
+        fields = INFO_MM if kind == AGENT_MM else INFO_EXE
+        rows.append([bool(isf) for _, isf in fields] + [False] * (INFO_AGENT_WORDS - len(fields)))
+    return torch.tensor(rows, dtype=torch.bool)
+
+
+def reduce_steps(rewards, info_words: torch.Tensor, done_all: torch.Tensor, layout,
+                 stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The accumulators of hftlob_env_rollout_eval from per-step outputs, as a sequential float64
+    loop over the steps (every word is one plain sum in step order; a widened float32 / int32
+    squares exactly), on the inputs' device.
+
+    rewards: float32 [T, E, n_agents], or the per-type list ``rollout(per_step=True)`` returns.
+    info_words: the raw info record, int32 [T, E, info_words] (``env.last_info_words`` of a
+    per_step rollout, reshaped; [T * E, info_words] is accepted).  done_all: bool [T, E].
+    layout: the env's ``EnvLayout``.  stats: float64 [E, n_agents, EVAL_WORDS] to continue from
+    (not modified); None starts from zeros.  Returns the new stats tensor."""
+    if not isinstance(rewards, torch.Tensor):
+        rewards = torch.cat([x.reshape(x.shape[0], x.shape[1], -1) for x in rewards], dim=2)
+    T, E, A = rewards.shape
+    if A != len(layout.agent_kinds) or rewards.dtype != torch.float32:
+        raise ValueError(f"rewards must be float32 [T, E, {len(layout.agent_kinds)}]")
+    if info_words.dtype != torch.int32 or info_words.numel() != T * E * layout.info_words:
+        raise ValueError(f"info_words must be int32 [T, E, {layout.info_words}]")
+    if tuple(done_all.shape) != (T, E):
+        raise ValueError("done_all must be [T, E]")
+    dev = rewards.device
+    st = torch.zeros((E, A, EVAL_WORDS), dtype=torch.float64, device=dev) if stats is None else stats.clone()
+    if tuple(st.shape) != (E, A, EVAL_WORDS) or st.dtype != torch.float64 or st.device != dev:
+        raise ValueError(f"stats must be float64 [{E}, {A}, {EVAL_WORDS}] on {dev}")
+    iw = info_words.reshape(T, E, layout.info_words)[:, :, INFO_WORLD_WORDS:INFO_WORLD_WORDS + A * INFO_AGENT_WORDS]
+    iw = iw.reshape(T, E, A, INFO_AGENT_WORDS).contiguous()
+    isf = _float_words(layout).to(dev)
+    x = torch.empty((T, E, A, N_QUANT), dtype=torch.float64, device=dev)
+    x[..., 0] = rewards.to(torch.float64)
+    x[..., 1:] = torch.where(isf, iw.view(torch.float32).to(torch.float64), iw.to(torch.float64))
+    x2 = x * x
+    done = done_all.to(device=dev, dtype=torch.bool)
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    for t in range(T):
+        d = done[t][:, None]                                   # [E, 1] over the agents
+        st[:, :, W_STEPS] += 1.0
+        st[:, :, W_EPISODES] += d.to(torch.float64)
+        run_sum = st[:, :, W_RUN_SUM] + x[t, :, :, 0]
+        run_len = st[:, :, W_RUN_LEN] + 1.0
+        for w, v in ((W_EP_SUM, run_sum), (W_EP_SUM2, run_sum * run_sum), (W_EP_LEN, run_len),
+                     (W_EP_LEN2, run_len * run_len)):
+            st[:, :, w] = torch.where(d, st[:, :, w] + v, st[:, :, w])
+        st[:, :, W_RUN_SUM] = torch.where(d, zero, run_sum)
+        st[:, :, W_RUN_LEN] = torch.where(d, zero, run_len)
+        st[:, :, W_STEP_Q:W_END_INFO:2] += x[t]
+        st[:, :, W_STEP_Q + 1:W_END_INFO:2] += x2[t]
+        d3 = d[:, :, None]
+        st[:, :, W_END_INFO::2] = torch.where(d3, st[:, :, W_END_INFO::2] + x[t, :, :, 1:], st[:, :, W_END_INFO::2])
+        st[:, :, W_END_INFO + 1::2] = torch.where(d3, st[:, :, W_END_INFO + 1::2] + x2[t, :, :, 1:],
+                                                  st[:, :, W_END_INFO + 1::2])
+    return st
+
+
+def _mean_std(n: float, s: float, s2: float) -> Dict[str, float]:
+    """mean and population standard deviation of n values with sum s and sum of squares s2
+    (NaN for n = 0; a variance that rounds below 0 counts as 0)."""
+    if n <= 0:
+        return {"mean": math.nan, "std": math.nan}
+    m = s / n
+    return {"mean": m, "std": math.sqrt(max(s2 / n - m * m, 0.0))}
+
+
+class EvalStats:
+    """A stats tensor (float64 [E, n_agents, EVAL_WORDS]) read per agent type.  Reductions over
+    the envs and a type's agents are plain float64 sums of the accumulator words; a mean or
+    standard deviation over zero values is NaN."""
+
+    def __init__(self, stats: torch.Tensor, layout):
+        if stats.dim() != 3 or stats.shape[1] != len(layout.agent_kinds) or stats.shape[2] != EVAL_WORDS \
+                or stats.dtype != torch.float64:
+            raise ValueError(f"stats must be float64 [E, {len(layout.agent_kinds)}, {EVAL_WORDS}]")
+        self.stats = stats
+        self.layout = layout
+        self.n_types = max(layout.agent_types) + 1
+        self._tot = [stats[:, [a for a, t in enumerate(layout.agent_types) if t == i]].sum(dim=(0, 1)).cpu().tolist()
+                     for i in range(self.n_types)]
+
+    def fields(self, t: int) -> List[str]:
+        """the info field names of type t (layout.INFO_MM / INFO_EXE)"""
+        kind = self.layout.agent_kinds[self.layout.agent_types.index(t)]
+        return [n for n, _ in (INFO_MM if kind == AGENT_MM else INFO_EXE)]
+
+    def steps(self, t: int) -> int:
+        """agent-steps tallied (envs x agents of the type x steps)"""
+        return int(self._tot[t][W_STEPS])
+
+    def episodes(self, t: int) -> int:
+        """episodes completed, counted per agent of the type"""
+        return int(self._tot[t][W_EPISODES])
+
+    def total_dones(self) -> int:
+        """the envs' global dones (the reference's total_dones: done["__all__"] summed)"""
+        return int(self.stats[:, 0, W_EPISODES].sum().item())
+
+    def _q(self, t: int, n: float, w: int) -> Dict[str, float]:
+        return _mean_std(n, self._tot[t][w], self._tot[t][w + 1])
+
+    def reward(self, t: int) -> Dict[str, float]:
+        return self._q(t, self._tot[t][W_STEPS], W_STEP_Q)
+
+    def info(self, t: int) -> Dict[str, Dict[str, float]]:
+        """every info field over all steps"""
+        return {n: self._q(t, self._tot[t][W_STEPS], W_STEP_Q + 2 * (1 + k)) for k, n in enumerate(self.fields(t))}
+
+    def info_at_episode_end(self, t: int) -> Dict[str, Dict[str, float]]:
+        """every info field at the episodes' last steps"""
+        return {n: self._q(t, self._tot[t][W_EPISODES], W_END_INFO + 2 * k) for k, n in enumerate(self.fields(t))}
+
+    def episode_reward(self, t: int) -> Dict[str, float]:
+        """the completed episodes' reward sums"""
+        return self._q(t, self._tot[t][W_EPISODES], W_EP_SUM)
+
+    def episode_length(self, t: int) -> Dict[str, float]:
+        return self._q(t, self._tot[t][W_EPISODES], W_EP_LEN)
+
+    def summary(self) -> dict:
+        """The numbers baseline_only_JAXMARL.py prints and logs, per agent type."""
+        types = []
+        for t in range(self.n_types):
+            r = self.reward(t)
+            types.append({"avg_reward": r["mean"], "std_reward": r["std"], "steps": self.steps(t),
+                          "episodes": self.episodes(t), "info": self.info(t),
+                          "episode_reward": self.episode_reward(t), "episode_length": self.episode_length(t),
+                          "info_at_episode_end": self.info_at_episode_end(t)})
+        return {"total_dones": self.total_dones(), "types": types}
+
+
+def fixed_action_row(env, fixed_actions: Sequence) -> torch.Tensor:
+    """FIXED_ACTIONS (one entry per agent type: an int, or a list of one int as the reference's
+    configs write it) -> the int32 [action_words] row of ``rollout_eval(fixed=True)``: every agent
+    of a type, and every word of a MultiDiscrete space, takes the type's action."""
+    counts = env.multi_agent_config.number_of_agents_per_type
+    if len(fixed_actions) != len(counts):
+        raise ValueError(f"fixed_actions must hold one entry per agent type ({len(counts)}), got {len(fixed_actions)}")
+    row = []
+    for t, (a, n, wd) in enumerate(zip(fixed_actions, counts, env.action_widths)):
+        if isinstance(a, (list, tuple)):
+            if len(a) != 1:
+                raise NotImplementedError(
+                    f"agent type {t}: {len(a)} fixed actions; the reference draws one of them uniformly per step "
+                    "(JAX's categorical), which is not implemented: give one action per agent type")
+            a = a[0]
+        row += [int(a)] * (n * wd)
+    return torch.tensor(row, dtype=torch.int32, device=env.device)
+
+
+def eval_keys(rng: torch.Tensor, n_envs: int, n_steps: int, partitionable: bool):
+    """n_steps of the script's step-key chain from the carried key ``rng`` (int32 [1, 2], device):
+    per step ``rng, _ = split(rng)`` (the unused action sample) and ``rng, _rng = split(rng)``, then
+    ``split(_rng, n_envs)`` for all the steps at once.  Returns (rng', keys [n_steps, n_envs, 2])."""
+    from .env import split_keys
+    sub = []
+    for _ in range(n_steps):
+        rng = split_keys(rng, 2, partitionable)[:, 0].contiguous()
+        pair = split_keys(rng, 2, partitionable)
+        rng = pair[:, 0].contiguous()
+        sub.append(pair[:, 1])
+    return rng, split_keys(torch.cat(sub).contiguous(), n_envs, partitionable)
+
+
+def evaluate_fixed_actions(env, fixed_actions: Sequence, n_envs: int, n_steps: int, seed: int,
+                           chunk: int = 256) -> EvalStats:
+    """baseline_only_JAXMARL.py's evaluation: reset ``n_envs`` envs, step them ``n_steps`` times
+    with one fixed action per agent type, and reduce.  The keys follow the shape of the script's
+    chain from ``PRNGKey(seed)``: ``rng, _rng = split(rng)`` and ``split(_rng, n_envs)`` for the
+    reset, then :func:`eval_keys` per step, generated ``chunk`` steps at a time on the device; one
+    ``rollout_eval(fixed=True)`` launch per chunk carries the stats over."""
+    from .env import split_keys
+    if n_envs < 1 or n_steps < 1 or chunk < 1:
+        raise ValueError("n_envs, n_steps and chunk must be >= 1")
+    row = fixed_action_row(env, fixed_actions)
+    part = bool(env.cfg_c.prng_partitionable)
+    params = env.default_params
+    rng = torch.tensor([[0, int(seed) & 0xFFFFFFFF]], dtype=torch.int64).to(torch.int32).to(env.device)
+    pair = split_keys(rng, 2, part)
+    rng = pair[:, 0].contiguous()
+    _, state = env.reset(split_keys(pair[:, 1].contiguous(), n_envs, part)[0], params)
+    stats = None
+    for t0 in range(0, n_steps, chunk):
+        rng, keys = eval_keys(rng, n_envs, min(chunk, n_steps - t0), part)
+        stats = env.rollout_eval(keys, state, row, params, stats=stats, fixed=True)[-1]
+    return EvalStats(stats, env.layout)
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m hftlob.evaluate", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--env-config", required=True, help="a built-in config name, or the path of a config .json")
+    ap.add_argument("--fixed-actions", required=True,
+                    help="one action per agent type, comma-separated (the reference's FIXED_ACTIONS)")
+    ap.add_argument("--envs", type=int, required=True)
+    ap.add_argument("--steps", type=int, required=True)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--chunk", type=int, default=256, help="steps per launch")
+    ap.add_argument("--data-msgs", type=int, default=400_000, help="length of the synthetic message day")
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args(argv)
+    from .config_io import builtin_config, load_config_from_file
+    from .data.synthetic import generate_day
+    from .env import MARLEnv
+    cfg = load_config_from_file(args.env_config) if os.path.exists(args.env_config) else builtin_config(args.env_config)
+    w = cfg.world_config
+    day = generate_day(n_msgs=args.data_msgs, snap_every=w.n_data_msg_per_step * w.start_resolution)
+    env = MARLEnv(None, cfg, data=day, device=args.device, return_info=False, persistent_outputs=True)
+    actions = [int(x) for x in args.fixed_actions.split(",")]
+    ev = evaluate_fixed_actions(env, actions, args.envs, args.steps, args.seed, args.chunk)
+    out = {"env_config": args.env_config, "fixed_actions": actions, "envs": args.envs, "steps": args.steps,
+           "seed": args.seed}
+    out.update(ev.summary())
+    print(json.dumps(out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
