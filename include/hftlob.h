@@ -30,6 +30,9 @@
  *   hftlob_sample_actions<- jaxen/Speed_test.py:166-177 (per-env random actions
  *                           via gymnax Discrete.sample = jax.random.randint).
  *   hftlob_split_keys    <- jax.random.split(key, n) (threefry2x32), batched.
+ *   hftlob_gru_scan_fwd / hftlob_gru_scan_bwd <- jaxrl/MARL/ippo_rnn_JAXMARL.py:53-78 ScannedRNN
+ *                           (the nn.scan of a GRUCell whose carry is reset where done is set) and
+ *                           its gradient through time, over a whole [T, B] sequence batch.
  */
 #ifndef HFTLOB_H
 #define HFTLOB_H
@@ -452,6 +455,37 @@ int hftlob_sample_actions(const hftlob_env_cfg* cfg /*[host]*/, int n_env, const
  * out[e][j] = split(keys[e], n)[j]; out [n_env][n][2]. */
 int hftlob_split_keys(int n_env, int n, int partitionable, const uint32_t* keys,
                       uint32_t* out, void* stream);
+
+/* Fused GRU sequence scan of the learner (ScannedRNN, jaxrl/MARL/ippo_rnn_JAXMARL.py:53-78), float32.
+ * gi [T][B][3H] is the input projection x W_ih^T + b_ih in gate order (r, z, n), computed by the
+ * caller over all T at once; w_hh [3H][H], b_hh [3H]; done [T][B] bytes (non-zero: the carry entering
+ * step t is reset).  With h_prev(t) = done[t] ? 0 : (t ? hseq[t-1] : h0), step t is
+ *     gh = h_prev(t) . w_hh^T + b_hh
+ *     r = sigmoid(gi_r + gh_r)   z = sigmoid(gi_z + gh_z)   n = tanh(gi_n + r * gh_n)
+ *     hseq[t] = (1 - z) * n + z * h_prev(t)
+ * hseq [T][B][H].  gates, when not NULL, receives (r, z, n, gh_n) of every step as [T][B][4H] (four
+ * blocks of H), which is what the backward operator reads; NULL skips those stores and changes no
+ * bit of hseq.  One launch per scan: a workgroup owns 16 batch rows for all T steps, and no workgroup
+ * waits on another.  H must be 64, 128 or 256 (else HFTLOB_ESHAPE); T >= 1, B >= 1 (rows past B in
+ * the last 16-row tile are neither read nor written). */
+int hftlob_gru_scan_fwd(int T, int B, int H, const float* gi, const float* h0 /*[B][H]*/, const uint8_t* done,
+                        const float* w_hh, const float* b_hh, float* hseq, float* gates /* or NULL */,
+                        void* stream);
+
+/* The scan's gradient through time from d_hseq [T][B][H] and the forward's hseq and gates:
+ * for t = T-1 .. 0, carry = 0 at the start,
+ *     dh = d_hseq[t] + carry
+ *     dn = dh * (1 - z) * (1 - n^2)     dz = dh * (h_prev(t) - n) * z * (1 - z)
+ *     dr = dn * gh_n * r * (1 - r)
+ *     d_gi[t] = (dr, dz, dn)            d_gh[t] = (dr, dz, dn * r)
+ *     carry = done[t] ? 0 : dh * z + d_gh[t] . w_hh
+ * and d_h0 [B][H] is the carry after t = 0.  d_gi [T][B][3H]; d_gh_n [T][B][H] is dn * r, so that
+ * d_gh = (d_gi_r, d_gi_z, d_gh_n).  The weight and bias gradients are left to the caller, as one
+ * GEMM and one reduction over all T: d_w_hh = d_gh[T B, 3H]^T . h_prev[T B, H], d_b_hh = sum d_gh.
+ * The same sizes, launch shape and codes as the forward operator; no pointer may be NULL. */
+int hftlob_gru_scan_bwd(int T, int B, int H, const float* d_hseq, const float* hseq, const float* gates,
+                        const float* h0, const uint8_t* done, const float* w_hh, float* d_gi, float* d_gh_n,
+                        float* d_h0, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,7 @@
 #include <limits.h>
 
 #include "../../include/hftlob.h"
+#include "hftlob_internal.h"
 
 typedef int32_t i32;
 typedef uint32_t u32;
@@ -4422,10 +4423,11 @@ HFTLOB_ROLL_KB(extern, 1) HFTLOB_ROLL_KB(extern, 0)
 
 // ================================================================ C ABI
 static thread_local char g_err[256] = "";
-static int fail(int code, const char* msg) {
+int hftlob_fail(int code, const char* msg) {  // (hftlob_internal.h: gru_scan.hip reports through it too)
     snprintf(g_err, sizeof g_err, "%s", msg);
     return code;
 }
+static int fail(int code, const char* msg) { return hftlob_fail(code, msg); }
 static int slot_sets(int n) { return n <= 64 ? 1 : (n <= 128 ? 2 : 4); }
 
 extern "C" {

@@ -26,7 +26,7 @@ EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob
            "hftlob_env_step", "hftlob_env_step_sampled", "hftlob_env_rollout_sampled", "hftlob_rollout_prepare",
            "hftlob_env_rollout_actions", "hftlob_env_rollout_eval",
            "hftlob_env_lds_bytes", "hftlob_env_launch_info",
-           "hftlob_sample_actions", "hftlob_split_keys")
+           "hftlob_sample_actions", "hftlob_split_keys", "hftlob_gru_scan_fwd", "hftlob_gru_scan_bwd")
 
 _lib = None
 
@@ -76,6 +76,10 @@ def lib() -> C.CDLL:
     L.hftlob_sample_actions.restype = i32
     L.hftlob_split_keys.argtypes = [i32, i32, i32, vp, vp, vp]
     L.hftlob_split_keys.restype = i32
+    L.hftlob_gru_scan_fwd.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.hftlob_gru_scan_fwd.restype = i32
+    L.hftlob_gru_scan_bwd.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.hftlob_gru_scan_bwd.restype = i32
     if L.hftlob_version() != ABI_VERSION:
         raise RuntimeError(f"libhftlob ABI {L.hftlob_version()} != {ABI_VERSION}")
     _lib = L

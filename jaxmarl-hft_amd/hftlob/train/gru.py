@@ -1,0 +1,146 @@
+"""The learner's GRU sequence scan (ScannedRNN, ippo_rnn_JAXMARL.py:53-78) as two engine
+operators and their autograd wrapper.
+
+``gru_scan_reference`` / ``gru_scan_backward_reference`` restate ``hftlob_gru_scan_fwd`` /
+``hftlob_gru_scan_bwd`` (include/hftlob.h) in torch, in whatever float type they are given: they
+are the spec of the kernels and what the tests compare against.  ``gru_scan`` is the fused path:
+one HIP launch per direction, the weight and bias gradients formed by torch as one GEMM and one
+reduction over all T.
+
+Notation: ``gi`` [T, B, 3H] is the input projection in gate order (r, z, n), ``done`` [T, B]
+resets the carry entering step t, ``h_prev(t) = done[t] ? 0 : (t ? hseq[t-1] : h0)``, and
+``gates`` [T, B, 4H] holds (r, z, n, gh_n) of every step.
+"""
+from __future__ import annotations
+
+import torch
+
+from .. import _lib
+
+SUPPORTED_HIDDEN = (64, 128, 256)   # the kernels' template instantiations (csrc/gru_scan.hip)
+
+
+def gru_scan_supported(hidden: int) -> bool:
+    """Whether the fused scan has a kernel for this hidden size (no GPU needed to ask)."""
+    return int(hidden) in SUPPORTED_HIDDEN
+
+
+def _h_prev(hseq, h0, done):
+    """h_prev(t) for every t, [T, B, H]."""
+    prev = torch.cat([h0[None], hseq[:-1]], 0)
+    return torch.where(done.bool()[..., None], torch.zeros_like(prev), prev)
+
+
+def gru_scan_reference(gi, h0, done, w_hh, b_hh):
+    """hftlob_gru_scan_fwd: (hseq [T, B, H], gates [T, B, 4H])."""
+    done = done.bool()
+    h, hs, gs = h0, [], []
+    for t in range(gi.shape[0]):
+        h = torch.where(done[t][:, None], torch.zeros_like(h), h)
+        ir, iz, i_n = gi[t].chunk(3, -1)
+        hr, hz, hn = (h @ w_hh.t() + b_hh).chunk(3, -1)
+        r = torch.sigmoid(ir + hr)
+        z = torch.sigmoid(iz + hz)
+        n = torch.tanh(i_n + r * hn)
+        h = (1.0 - z) * n + z * h
+        hs.append(h)
+        gs.append(torch.cat([r, z, n, hn], -1))
+    return torch.stack(hs), torch.stack(gs)
+
+
+def gru_scan_backward_reference(d_hseq, hseq, gates, h0, done, w_hh):
+    """hftlob_gru_scan_bwd: (d_gi [T, B, 3H], d_gh_n [T, B, H], d_h0 [B, H])."""
+    done = done.bool()
+    hp = _h_prev(hseq, h0, done)
+    carry = torch.zeros_like(h0)
+    d_gi, d_ghn = [None] * len(hseq), [None] * len(hseq)
+    for t in range(len(hseq) - 1, -1, -1):
+        r, z, n, ghn = gates[t].chunk(4, -1)
+        dh = d_hseq[t] + carry
+        dn = dh * (1.0 - z) * (1.0 - n * n)
+        dz = dh * (hp[t] - n) * z * (1.0 - z)
+        dr = dn * ghn * r * (1.0 - r)
+        d_gi[t] = torch.cat([dr, dz, dn], -1)
+        d_ghn[t] = dn * r
+        dh_prev = dh * z + torch.cat([dr, dz, d_ghn[t]], -1) @ w_hh
+        carry = torch.where(done[t][:, None], torch.zeros_like(dh_prev), dh_prev)
+    return torch.stack(d_gi), torch.stack(d_ghn), carry
+
+
+def weight_grads(d_gi, d_gh_n, hseq, h0, done):
+    """(d_w_hh [3H, H], d_b_hh [3H]) from the backward operator's outputs: the parts of the
+    gradient that are one GEMM and one reduction over all T."""
+    H = hseq.shape[-1]
+    d_gh = torch.cat([d_gi[..., :2 * H], d_gh_n], -1).reshape(-1, 3 * H)
+    return d_gh.t() @ _h_prev(hseq, h0, done).reshape(-1, H), d_gh.sum(0)
+
+
+def _f32(t):
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _u8(done):
+    """done as the operators' bytes; a bool tensor is reinterpreted, not copied."""
+    done = done.detach().contiguous()
+    return done.view(torch.uint8) if done.dtype == torch.bool else done.to(torch.uint8)
+
+
+def scan_forward(gi, h0, done, w_hh, b_hh, save_gates: bool = True):
+    """hftlob_gru_scan_fwd on device tensors: (hseq, gates or None)."""
+    T, B, H3 = gi.shape
+    H = H3 // 3
+    gi, h0, w_hh, b_hh = _f32(gi), _f32(h0), _f32(w_hh), _f32(b_hh)
+    done = _u8(done)
+    ptrs = [_lib.ptr(x) for x in (gi, h0, done, w_hh, b_hh)]   # (a CPU tensor raises here)
+    if h0.shape != (B, H) or done.shape != (T, B) or w_hh.shape != (3 * H, H) or b_hh.shape != (3 * H,):
+        raise ValueError(f"gru_scan: shapes gi {tuple(gi.shape)}, h0 {tuple(h0.shape)}, done {tuple(done.shape)}, "
+                         f"w_hh {tuple(w_hh.shape)}, b_hh {tuple(b_hh.shape)} do not agree")
+    hseq = torch.empty((T, B, H), dtype=torch.float32, device=gi.device)
+    gates = torch.empty((T, B, 4 * H), dtype=torch.float32, device=gi.device) if save_gates else None
+    _lib.check(_lib.lib().hftlob_gru_scan_fwd(T, B, H, *ptrs, _lib.ptr(hseq), _lib.ptr(gates),
+                                              _lib.stream_ptr(device=gi.device)))
+    return hseq, gates
+
+
+def scan_backward(d_hseq, hseq, gates, h0, done, w_hh):
+    """hftlob_gru_scan_bwd on device tensors: (d_gi, d_gh_n, d_h0)."""
+    T, B, H = hseq.shape
+    d_hseq, hseq, gates, h0, w_hh = _f32(d_hseq), _f32(hseq), _f32(gates), _f32(h0), _f32(w_hh)
+    done = _u8(done)
+    ptrs = [_lib.ptr(x) for x in (d_hseq, hseq, gates, h0, done, w_hh)]
+    if d_hseq.shape != (T, B, H) or gates.shape != (T, B, 4 * H) or h0.shape != (B, H) or done.shape != (T, B) \
+            or w_hh.shape != (3 * H, H):
+        raise ValueError("gru_scan backward: shapes do not agree")
+    d_gi = torch.empty((T, B, 3 * H), dtype=torch.float32, device=hseq.device)
+    d_gh_n = torch.empty((T, B, H), dtype=torch.float32, device=hseq.device)
+    d_h0 = torch.empty((B, H), dtype=torch.float32, device=hseq.device)
+    _lib.check(_lib.lib().hftlob_gru_scan_bwd(T, B, H, *ptrs, _lib.ptr(d_gi), _lib.ptr(d_gh_n), _lib.ptr(d_h0),
+                                              _lib.stream_ptr(device=hseq.device)))
+    return d_gi, d_gh_n, d_h0
+
+
+class GRUScan(torch.autograd.Function):
+    """hseq = gru_scan(gi, h0, done, w_hh, b_hh), differentiable in gi, h0, w_hh and b_hh."""
+
+    @staticmethod
+    def forward(ctx, gi, h0, done, w_hh, b_hh):
+        need = any(ctx.needs_input_grad)
+        hseq, gates = scan_forward(gi, h0, done, w_hh, b_hh, save_gates=need)
+        if need:
+            ctx.save_for_backward(hseq, gates, _f32(h0), done, _f32(w_hh))
+        return hseq
+
+    @staticmethod
+    def backward(ctx, d_hseq):
+        hseq, gates, h0, done, w_hh = ctx.saved_tensors
+        # the stream is taken inside the call: autograd runs this under the forward's stream guard
+        d_gi, d_gh_n, d_h0 = scan_backward(d_hseq, hseq, gates, h0, done, w_hh)
+        d_w, d_b = (None, None)
+        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+            d_w, d_b = weight_grads(d_gi, d_gh_n, hseq, h0, done)
+        return d_gi, d_h0, None, d_w, d_b
+
+
+def gru_scan(gi, h0, done, w_hh, b_hh):
+    """The fused scan: hseq [T, B, H] (float32, on the device of ``gi``)."""
+    return GRUScan.apply(gi, h0, done, w_hh, b_hh)

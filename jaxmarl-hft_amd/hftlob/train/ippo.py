@@ -42,6 +42,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..env import MARLEnv, split_keys
+from .gru import SUPPORTED_HIDDEN, gru_scan, gru_scan_supported
 
 
 def _per_type(v, n: int) -> list:
@@ -56,7 +57,7 @@ def default_config(**kw) -> Dict:
          "TOTAL_TIMESTEPS": 5e8, "UPDATE_EPOCHS": 4, "NUM_MINIBATCHES": 4, "GAMMA": [0.999999999, 0.999],
          "GAE_LAMBDA": [0.85, 0.9], "CLIP_EPS": 0.2, "ENT_COEF": [0.01, 0.01], "VF_COEF": [0.5, 0.5],
          "MAX_GRAD_NORM": [0.5, 0.5], "ANNEAL_LR": [True, True], "NUM_AGENTS_PER_TYPE": [1, 1], "SEED": 2,
-         "CUDA_GRAPHS": True}
+         "CUDA_GRAPHS": True, "FUSED_GRU": False}
     c.update(kw)
     return c
 
@@ -73,6 +74,7 @@ class ActorCriticRNN(nn.Module):
             nn.init.orthogonal_(m.weight, g)
             nn.init.zeros_(m.bias)
         self.hidden = hidden
+        self.fused = False   # forward's scan as one HIP launch per direction (train.gru.gru_scan); the trainer sets it
 
     def step(self, h: torch.Tensor, obs: torch.Tensor, done: torch.Tensor):
         """One time step for a batch of actors: (new carry, logits, value)."""
@@ -81,17 +83,14 @@ class ActorCriticRNN(nn.Module):
         v = self.critic2(F.relu(self.critic1(h))).squeeze(-1)
         return h, self.actor2(F.relu(self.actor1(h))), v
 
-    def forward(self, h0: torch.Tensor, obs: torch.Tensor, dones: torch.Tensor):
-        """A sequence [T, B, ...] from carry h0 (the ScannedRNN scan): logits [T, B, A], values [T, B].
-        The same cell as ``step``; the input-side GEMMs (embedding, the GRU's input
-        projection, both heads) run once over all T, only h @ W_hh stays in the scan."""
+    @staticmethod
+    def scan_loop(gi_all, h0, dones, w_hh, b_hh):
+        """The ScannedRNN scan as a loop over T, one GEMM and the gate math per step: hseq [T, B, H]."""
         # unbind / chunk (not slicing): their backward concatenates the per-step grads once,
         # where a slice's backward would zero-fill and add a whole [T, B, 3H] grad per step
-        gis = F.linear(F.relu(self.embed(obs)), self.gru.weight_ih, self.gru.bias_ih).unbind(0)  # (r, z, n)
-        w_hh, b_hh = self.gru.weight_hh, self.gru.bias_hh
         h = h0
         hs = []
-        for t, gi in enumerate(gis):
+        for t, gi in enumerate(gi_all.unbind(0)):
             h = torch.where(dones[t][:, None], torch.zeros_like(h), h)
             ir, iz, i_n = gi.chunk(3, -1)
             hr, hz, hn = F.linear(h, w_hh, b_hh).chunk(3, -1)
@@ -100,7 +99,16 @@ class ActorCriticRNN(nn.Module):
             n = torch.tanh(i_n + r * hn)
             h = (1.0 - z) * n + z * h
             hs.append(h)
-        hseq = torch.stack(hs)
+        return torch.stack(hs)
+
+    def forward(self, h0: torch.Tensor, obs: torch.Tensor, dones: torch.Tensor):
+        """A sequence [T, B, ...] from carry h0 (the ScannedRNN scan): logits [T, B, A], values [T, B].
+        The same cell as ``step``; the input-side GEMMs (embedding, the GRU's input
+        projection, both heads) run once over all T, only h @ W_hh stays in the scan: the loop
+        of ``scan_loop``, or with ``fused`` set one HIP launch forward and one backward."""
+        gi_all = F.linear(F.relu(self.embed(obs)), self.gru.weight_ih, self.gru.bias_ih)  # [T, B, 3H], (r, z, n)
+        scan = gru_scan if self.fused else self.scan_loop
+        hseq = scan(gi_all, h0, dones, self.gru.weight_hh, self.gru.bias_hh)
         return self.actor2(F.relu(self.actor1(hseq))), self.critic2(F.relu(self.critic1(hseq))).squeeze(-1)
 
 
@@ -196,6 +204,13 @@ class IPPOTrainer:
         torch.manual_seed(c["SEED"])  # the same initial parameters on every rank
         self.nets = [ActorCriticRNN(env.observation_spaces[i].shape[0], env.action_spaces[i].n, c["FC_DIM_SIZE"],
                                     c["GRU_HIDDEN_DIM"]).to(self.device) for i in range(nt)]
+        # FUSED_GRU: the minibatch step's sequence scan through the fused operators (GPU only; off: the loop)
+        if c.get("FUSED_GRU", False):
+            if not gru_scan_supported(c["GRU_HIDDEN_DIM"]):
+                raise ValueError(f"FUSED_GRU needs GRU_HIDDEN_DIM in {list(SUPPORTED_HIDDEN)}, "
+                                 f"got {c['GRU_HIDDEN_DIM']}")
+            for n in self.nets:
+                n.fused = self.device.type == "cuda"
         # HIP-graph minibatch steps: single process on the GPU (the grad all-reduce stays eager)
         self.graphs = bool(c.get("CUDA_GRAPHS", False)) and self.device.type == "cuda" and world == 1
         if self.graphs:  # capturable Adam: step counter and lr live on the device
@@ -408,6 +423,7 @@ def main(argv=None) -> None:
     ap.add_argument("--env-config", default="2_player_fq_fqc", help="JSON path or builtin config name")
     ap.add_argument("--updates", type=int, default=2)
     ap.add_argument("--envs", type=int, default=None)
+    ap.add_argument("--fused-gru", action="store_true", help="the PPO update's GRU scan as the fused HIP operators")
     ap.add_argument("--data", default=None, help="'lobster' to load world_config.dataPath (else synthetic)")
     a = ap.parse_args(argv)
     c = default_config()
@@ -416,6 +432,8 @@ def main(argv=None) -> None:
             c.update({k: v for k, v in yaml.safe_load(f).items() if k in c})
     if a.envs:
         c["NUM_ENVS"] = a.envs
+    if a.fused_gru:
+        c["FUSED_GRU"] = True
     cfg = (load_config_from_file(a.env_config) if a.env_config.endswith((".json", ".yaml"))
            else builtin_config(a.env_config))
     env = MARLEnv(None, cfg, data=a.data, return_info=False, persistent_outputs=True)

@@ -1,4 +1,9 @@
-"""Time the IPPO learner's phases on the GPU (rollout vs PPO epochs) at the metric config."""
+"""Time the IPPO learner's phases on the GPU (rollout vs PPO epochs) at the metric config.
+
+    python tools/train_timing.py [--graph] [--fused-gru]
+
+--graph: CUDA_GRAPHS (the rollout and each minibatch step replayed as HIP graphs);
+--fused-gru: FUSED_GRU (the minibatch step's GRU scan through hftlob_gru_scan_fwd / _bwd)."""
 import os
 import sys
 import time
@@ -20,7 +25,8 @@ def main():
     day = generate_day(n_msgs=100_000, seed=4, snap_every=w.n_data_msg_per_step * w.start_resolution)
     env = MARLEnv(None, cfg, data=day, return_info=False, persistent_outputs=True)
     graph = "--graph" in sys.argv
-    c = I.default_config(NUM_ENVS=4096, NUM_STEPS=64, TOTAL_TIMESTEPS=4096 * 64 * 50, CUDA_GRAPHS=graph)
+    c = I.default_config(NUM_ENVS=4096, NUM_STEPS=64, TOTAL_TIMESTEPS=4096 * 64 * 50, CUDA_GRAPHS=graph,
+                         FUSED_GRU="--fused-gru" in sys.argv)
     tr = I.IPPOTrainer(env, c)
     tr.update()
     torch.cuda.synchronize()
