@@ -33,6 +33,9 @@
  *   hftlob_gru_scan_fwd / hftlob_gru_scan_bwd <- jaxrl/MARL/ippo_rnn_JAXMARL.py:53-78 ScannedRNN
  *                           (the nn.scan of a GRUCell whose carry is reset where done is set) and
  *                           its gradient through time, over a whole [T, B] sequence batch.
+ *   hftlob_policy_step   <- jaxrl/MARL/ippo_rnn_JAXMARL.py:53-78, 183-256: one ActorCriticRNN step
+ *                           (embedding, GRU cell, critic and actor heads) with the rollout's
+ *                           pi.sample / log_prob (:590-600), for a batch of actors.
  */
 #ifndef HFTLOB_H
 #define HFTLOB_H
@@ -486,6 +489,46 @@ int hftlob_gru_scan_fwd(int T, int B, int H, const float* gi, const float* h0 /*
 int hftlob_gru_scan_bwd(int T, int B, int H, const float* d_hseq, const float* hseq, const float* gates,
                         const float* h0, const uint8_t* done, const float* w_hh, float* d_gi, float* d_gh_n,
                         float* d_h0, void* stream);
+
+/* Fused recurrent policy step: one ActorCriticRNN step (jaxrl/MARL/ippo_rnn_JAXMARL.py:53-78 ScannedRNN's
+ * cell, :183-256 SingleActionOutput and ActorCriticRNN) for a batch of B actors as one launch, float32.
+ * The weights are a host struct of device pointers in torch's nn.Linear / nn.GRUCell layouts
+ * ([out][in] rows; the GRU's gate order is r, z, n).  Per row b, with h_prev = done[b] ? 0 : h_in[b]:
+ *     x      = relu(obs . w_embed^T + b_embed)
+ *     gi     = x . w_ih^T + b_ih          gh = h_prev . w_hh^T + b_hh
+ *     r = sigmoid(gi_r + gh_r)   z = sigmoid(gi_z + gh_z)   n = tanh(gi_n + r * gh_n)
+ *     h      = (1 - z) * n + z * h_prev                     -> h_out
+ *     value  = relu(h . w_c1^T + b_c1) . w_c2^T + b_c2
+ *     logits = relu(h . w_a1^T + b_a1) . w_a2^T + b_a2
+ *     action : mode 1 = the first argmax of logits
+ *              mode 0 = the first argmax of logits + g
+ *     log_prob = logits[action] - max - log(sum exp(logits - max))
+ * the cell of hftlob_gru_scan_fwd.  g [B][A] is jax.random.gumbel(key, (B, A)) under the partitionable
+ * threefry (jax_threefry_partitionable; the legacy form is not built): with bits = y0 ^ y1 of
+ * threefry2x32(key, (0, b A + a)), f = bitcast((bits >> 9) | 0x3f800000) - 1,
+ * u = max(tiny, f (1 - tiny) + tiny) (tiny: float32's smallest normal) and g = -log(-log(u)), so mode 0
+ * is jax.random.categorical(key, logits), the reference's pi.sample(seed=_rng).  key is two device
+ * words, read in mode 0 only (NULL is allowed in mode 1).
+ * h_out may be h_in (in place).  logits [B][A] may be NULL, which changes no bit of the other outputs.
+ * Sizes: H and FC each 64, 128 or 256; 1 <= D <= 64; 1 <= A <= 16; B >= 1, else HFTLOB_ESHAPE; a
+ * required NULL pointer is HFTLOB_ENULL; a mode outside {0, 1}, or a w_ih, w_hh, w_c1, w_a1 or w_a2
+ * that is not 16-byte aligned, is HFTLOB_EINVAL.  A workgroup owns 16 rows and waits on no other; rows
+ * past B in the last tile are never written, and rows of w_a2 past A are never read.  The call never
+ * allocates and never synchronises: it runs on the caller's stream and can be captured in a HIP graph
+ * (the struct is copied at the call; the arrays it points to are read at every replay). */
+typedef struct {
+    const float *w_embed /*[FC][D]*/, *b_embed /*[FC]*/;
+    const float *w_ih /*[3H][FC]*/, *b_ih /*[3H]*/, *w_hh /*[3H][H]*/, *b_hh /*[3H]*/;
+    const float *w_c1 /*[FC][H]*/, *b_c1 /*[FC]*/, *w_c2 /*[1][FC]*/, *b_c2 /*[1]*/;
+    const float *w_a1 /*[H][H]*/, *b_a1 /*[H]*/, *w_a2 /*[A][H]*/, *b_a2 /*[A]*/;
+} hftlob_policy_weights;
+
+int hftlob_policy_step(int B, int D, int FC, int H, int A, const hftlob_policy_weights* w /*[host]*/,
+                       const float* obs /*[B][D]*/, const uint8_t* done /*[B]*/,
+                       const float* h_in /*[B][H]*/, float* h_out /*[B][H]; may be h_in*/,
+                       int mode, const uint32_t* key /*[2], device; mode 0 only*/,
+                       int32_t* action /*[B]*/, float* log_prob /*[B]*/, float* value /*[B]*/,
+                       float* logits /*[B][A] or NULL*/, void* stream);
 
 #ifdef __cplusplus
 }

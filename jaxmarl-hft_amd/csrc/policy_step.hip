@@ -1,0 +1,381 @@
+// Fused recurrent policy step for IPPO rollouts and policy evaluation (include/hftlob.h:
+// hftlob_policy_step), gfx950.
+//
+// One ActorCriticRNN step (jaxrl/MARL/ippo_rnn_JAXMARL.py:53-78, 183-256) for a batch of actors as
+// one launch: embedding, GRU cell, critic and actor heads, softmax, the sample (or the argmax) and
+// its log-probability.  It is shaped like k_gru_scan_fwd (gru_scan.hip): a workgroup owns a tile of
+// 16 batch rows, the M side of the f32-input 16x16x4 MFMA, and waits on no other workgroup.  Every
+// product is that MFMA, so every dot product is a k-ordered fmaf chain in float32.
+//
+// The layers chain through LDS, three padded [16][W + 4] buffers:
+//     bx   x = relu(embed)            then relu(critic1) once the gates are done
+//     bp   h_prev                     then relu(actor1)
+//     bh   obs (zero-padded to 64 k)  then h
+// with a barrier after the embedding, after the gates and after the two hidden head layers.
+//
+//   embedding  a wave takes column blocks w, w + NW, ... of x; k = D <= 64 is padded to 16 MFMAs, the
+//              B operand is w_embed read as dwords (its rows are D floats, not 16-byte aligned)
+//   gates      a wave owns CB blocks of 16 hidden indices j and computes gi and gh of the r, z and n
+//              columns of those j, so the gate math runs in registers on the accumulators
+//   heads      critic1 (FC columns) and actor1 (H columns) read the same h: their (FC + H) / 16
+//              column blocks are dealt over the waves, a wave's blocks run together on one A operand
+//   outputs    wave 0: logits = relu(actor1) . w_a2^T as one MFMA column block (A <= 16), then the
+//              softmax, the Gumbel noise and the argmax over 16-lane rows; wave 1: value, a 16-row
+//              dot product over FC reduced across the lane quarters
+//
+// The weights (about 2.1 MB at 256 / 256) stream from L2 as float4 per lane into register buffers
+// two chunks of 32 k ahead of the MFMAs that use them, with the forward scan's operand maps (lane
+// quarter q of chunk c has k = 32 c + 8 q + 0..7 for both operands).  The three lessons of the scan
+// hold here too: loads are unconditional at clamped indices, no branch sits between a prefetch and
+// its wait, and a sched_barrier keeps the loads where they are issued.  A stage's first chunks are
+// requested before the previous stage's epilogue and barrier.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/hftlob.h"
+#include "hftlob_internal.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32;
+
+constexpr int TILE = 16;  // batch rows per workgroup: the M of mfma_f32_16x16x4f32
+constexpr int PF = 2;     // weight chunks in flight per stream
+constexpr int DMAX = 64;  // obs columns in LDS (D <= 64, zero-padded)
+
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ f32x4 splat(float x) { return f32x4{x, x, x, x}; }
+__device__ __forceinline__ u32 rotl32(u32 x, int r) { return (x << r) | (x >> (32 - r)); }
+
+// threefry2x32 with 20 rounds (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3"), as JAX
+// runs it: returns y0 ^ y1, the partitionable random_bits word of counter (x0, x1)
+__device__ __forceinline__ u32 threefry_bits(u32 k0, u32 k1, u32 x0, u32 x1) {
+    const u32 ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
+    const int rot[2][4] = {{13, 15, 26, 6}, {17, 29, 16, 24}};
+    x0 += ks[0];
+    x1 += ks[1];
+#pragma unroll
+    for (int i = 1; i <= 5; ++i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            x0 += x1;
+            x1 = rotl32(x1, rot[(i - 1) & 1][j]) ^ x0;
+        }
+        x0 += ks[i % 3];
+        x1 += ks[(i + 1) % 3] + (u32)i;
+    }
+    return x0 ^ x1;
+}
+
+// jax.random.gumbel's float32 draw from one random word
+__device__ __forceinline__ float gumbel_from_bits(u32 bits) {
+    const float tiny = 1.17549435e-38f;  // float32's smallest normal
+    const float f = __uint_as_float((bits >> 9) | 0x3f800000u) - 1.0f;
+    const float u = fmaxf(tiny, f * (1.0f - tiny) + tiny);
+    return -logf(-logf(u));
+}
+
+// MFMA operand maps (16x16x4 f32): lane l gives A[row l & 15][k l >> 4] and B[k l >> 4][col l & 15];
+// accumulator register i of lane l is D[row 4 (l >> 4) + i][col l & 15].
+
+// the first PF chunks of N weight rows (wp[n] is the lane's row, already at its quarter's 8 q)
+template <int N>
+__device__ __forceinline__ void prefetch(f32x4 (&wv)[PF][N][2], const float* const (&wp)[N]) {
+#pragma unroll
+    for (int p = 0; p < PF; ++p)
+#pragma unroll
+        for (int n = 0; n < N; ++n) {
+            wv[p][n][0] = ld4(wp[n] + 32 * p);
+            wv[p][n][1] = ld4(wp[n] + 32 * p + 4);
+        }
+}
+
+// one chunk of 32 k: acc[n] += A (two float4 of the lane's LDS row) . wv[n], then the slot's refill
+template <int N>
+__device__ __forceinline__ void chunk(f32x4 (&acc)[N], f32x4 (&wv)[N][2], const float* ap, const float* const (&np)[N],
+                                      int noff) {
+    const f32x4 a[2] = {ld4(ap), ld4(ap + 4)};
+#pragma unroll
+    for (int s = 0; s < 8; ++s)
+#pragma unroll
+        for (int n = 0; n < N; ++n)
+            acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s >> 2][s & 3], wv[n][s >> 2][s & 3], acc[n], 0, 0, 0);
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        wv[n][0] = ld4(np[n] + noff);
+        wv[n][1] = ld4(np[n] + noff + 4);
+    }
+    __builtin_amdgcn_sched_barrier(0);  // the loads stay here: a chunk of MFMAs between issue and use
+}
+
+// acc[n] += A[16][K] . W_n^T over K in chunks of 32, wv holding the first PF chunks on entry.  The
+// prefetch is unconditional: the last PF chunks fetch the first PF chunks of wnext (the stream that
+// follows, or wp again where nothing follows; those are never used)
+template <int N, int K>
+__device__ __forceinline__ void stream(f32x4 (&acc)[N], f32x4 (&wv)[PF][N][2], const float* const (&wp)[N],
+                                       const float* const (&wnext)[N], const float* ap) {
+    constexpr int NCH = K / 32;
+    static_assert(NCH % PF == 0, "the k loop is unrolled by PF chunks");
+#pragma unroll 1
+    for (int ch = 0; ch < NCH - PF; ch += PF) {
+#pragma unroll
+        for (int p = 0; p < PF; ++p) chunk<N>(acc, wv[p], ap + 32 * (ch + p), wp, 32 * (ch + p + PF));
+    }
+#pragma unroll
+    for (int p = 0; p < PF; ++p) chunk<N>(acc, wv[p], ap + 32 * (NCH - PF + p), wnext, 32 * p);
+}
+
+template <int H, int FC>
+struct Shape {
+    static constexpr int CB = H == 256 ? 2 : 1;                   // hidden column blocks per wave
+    static constexpr int NW = H / 16 / CB;                        // waves
+    static constexpr int NT = 64 * NW;
+    static constexpr int NBE = (FC / 16 + NW - 1) / NW;           // embedding column blocks per wave
+    static constexpr int NBH = ((FC + H) / 16 + NW - 1) / NW;     // head column blocks per wave
+};
+
+template <int H, int FC>
+__global__ __launch_bounds__((Shape<H, FC>::NT)) void k_policy_step(
+    int B, int D, int A, hftlob_policy_weights W, const float* __restrict__ obs, const uint8_t* __restrict__ done,
+    const float* h_in, float* h_out, int mode, const u32* __restrict__ key, int32_t* __restrict__ action,
+    float* __restrict__ log_prob, float* __restrict__ value, float* __restrict__ logits) {
+    typedef Shape<H, FC> Sh;
+    constexpr int CB = Sh::CB, NW = Sh::NW, NT = Sh::NT, NBE = Sh::NBE, NBH = Sh::NBH;
+    constexpr int SX = FC + 4, SH = H + 4, NG = 3 * CB;
+    static_assert(H >= DMAX, "the obs tile lives in the h buffer");
+    __shared__ __attribute__((aligned(16))) float bx[TILE * SX];  // x, then relu(critic1)
+    __shared__ __attribute__((aligned(16))) float bp[TILE * SH];  // h_prev, then relu(actor1)
+    __shared__ __attribute__((aligned(16))) float bh[TILE * SH];  // obs, then h
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, li = l & 15, q = l >> 4;
+    const int b0 = blockIdx.x * TILE;
+
+    // the gates' W_ih rows and the embedding's B operands, requested before anything waits
+    int col[CB];
+    const float *wpi[NG], *wph[NG];
+#pragma unroll
+    for (int c = 0; c < CB; ++c) {
+        col[c] = (w * CB + c) * 16 + li;
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            wpi[c * 3 + g] = W.w_ih + (size_t)(g * H + col[c]) * FC + 8 * q;
+            wph[c * 3 + g] = W.w_hh + (size_t)(g * H + col[c]) * H + 8 * q;
+        }
+    }
+    f32x4 wg[PF][NG][2];
+    prefetch<NG>(wg, wpi);
+    float we[NBE][DMAX / 4];  // w_embed[col][4 s + q], zero past D
+#pragma unroll
+    for (int e = 0; e < NBE; ++e) {
+        const int ecol = min(w + NW * e, FC / 16 - 1) * 16 + li;
+#pragma unroll
+        for (int s = 0; s < DMAX / 4; ++s) {
+            const int k = 4 * s + q;
+            const float v = W.w_embed[(size_t)ecol * D + min(k, D - 1)];
+            we[e][s] = k < D ? v : 0.0f;
+        }
+    }
+
+    // the tile's obs and h_prev = done ? 0 : h_in, at clamped rows (a row past B repeats row B - 1 and
+    // is never stored)
+    for (int i = tid; i < TILE * DMAX; i += NT) {
+        const int row = i / DMAX, k = i % DMAX, b = min(b0 + row, B - 1);
+        const float v = obs[(size_t)b * D + min(k, D - 1)];
+        bh[row * SH + k] = k < D ? v : 0.0f;
+    }
+    for (int i = tid; i < TILE * H; i += NT) {
+        const int row = i / H, j = i % H, b = min(b0 + row, B - 1);
+        const float v = h_in[(size_t)b * H + j];
+        bp[row * SH + j] = done[b] ? 0.0f : v;
+    }
+    __syncthreads();
+
+    // x = relu(obs . w_embed^T + b_embed)
+#pragma unroll
+    for (int e = 0; e < NBE; ++e) {
+        const int blk = w + NW * e, ecol = min(blk, FC / 16 - 1) * 16 + li;
+        f32x4 acc = splat(W.b_embed[ecol]);
+#pragma unroll
+        for (int s = 0; s < DMAX / 4; ++s)
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(bh[li * SH + 4 * s + q], we[e][s], acc, 0, 0, 0);
+        if (blk < FC / 16) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) bx[(4 * q + i) * SX + ecol] = fmaxf(acc[i], 0.0f);
+        }
+    }
+    f32x4 gi[NG], gh[NG];
+#pragma unroll
+    for (int c = 0; c < CB; ++c)
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            gi[c * 3 + g] = splat(W.b_ih[g * H + col[c]]);
+            gh[c * 3 + g] = splat(W.b_hh[g * H + col[c]]);
+        }
+    __syncthreads();  // x complete; every read of obs is behind us
+
+    // gi = x . w_ih^T + b_ih and gh = h_prev . w_hh^T + b_hh of the wave's columns
+    stream<NG, FC>(gi, wg, wpi, wph, bx + li * SX + 8 * q);
+    stream<NG, H>(gh, wg, wph, wph, bp + li * SH + 8 * q);
+
+    // the heads' first chunks, in flight under the gate math.  Head block k < FC / 16 is a block of
+    // critic1's columns, the others are actor1's; a wave's block past the last repeats the last
+    int hblk[NBH], hcol[NBH];
+    const float* wpc[NBH];
+    float hbias[NBH];
+#pragma unroll
+    for (int n = 0; n < NBH; ++n) {
+        hblk[n] = w + NW * n;
+        const int blk = min(hblk[n], (FC + H) / 16 - 1);
+        const bool critic = blk < FC / 16;
+        hcol[n] = (critic ? blk : blk - FC / 16) * 16 + li;
+        wpc[n] = (critic ? W.w_c1 : W.w_a1) + (size_t)hcol[n] * H + 8 * q;
+        hbias[n] = (critic ? W.b_c1 : W.b_a1)[hcol[n]];
+    }
+    f32x4 wh[PF][NBH][2];
+    prefetch<NBH>(wh, wpc);
+    __builtin_amdgcn_sched_barrier(0);
+
+#pragma unroll
+    for (int c = 0; c < CB; ++c)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = 4 * q + i;
+            const float hp = bp[row * SH + col[c]];
+            const float r = sigmoidf_(gi[c * 3 + 0][i] + gh[c * 3 + 0][i]);
+            const float z = sigmoidf_(gi[c * 3 + 1][i] + gh[c * 3 + 1][i]);
+            const float n = tanhf(gi[c * 3 + 2][i] + r * gh[c * 3 + 2][i]);
+            const float h = (1.0f - z) * n + z * hp;
+            if (b0 + row < B) h_out[(size_t)(b0 + row) * H + col[c]] = h;
+            bh[row * SH + col[c]] = h;
+        }
+    __syncthreads();  // h complete; x and h_prev are dead
+
+    // relu(critic1) -> bx, relu(actor1) -> bp
+    f32x4 ha[NBH];
+#pragma unroll
+    for (int n = 0; n < NBH; ++n) ha[n] = splat(hbias[n]);
+    stream<NBH, H>(ha, wh, wpc, wpc, bh + li * SH + 8 * q);
+
+    // the logits' first chunks (wave 0 uses them), in flight under the stores and the barrier; rows
+    // of w_a2 past A repeat row A - 1 and their columns are masked below
+    const int arow = min(li, A - 1);
+    const float* wpa[1] = {W.w_a2 + (size_t)arow * H + 8 * q};
+    f32x4 wa[PF][1][2];
+    prefetch<1>(wa, wpa);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int n = 0; n < NBH; ++n) {
+        if (hblk[n] < (FC + H) / 16) {
+            float* dst = hblk[n] < FC / 16 ? bx + hcol[n] : bp + hcol[n];
+            const int S = hblk[n] < FC / 16 ? SX : SH;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dst[(4 * q + i) * S] = fmaxf(ha[n][i], 0.0f);
+        }
+    }
+    __syncthreads();  // both hidden head layers complete
+
+    if (w == 1) {  // value = relu(critic1) . w_c2^T + b_c2: lane quarter q sums a quarter of FC for row li
+        float v = 0.0f;
+        const float* xr = bx + li * SX + q * (FC / 4);
+        const float* wr = W.w_c2 + q * (FC / 4);
+#pragma unroll 8
+        for (int k = 0; k < FC / 4; ++k) v = fmaf(xr[k], wr[k], v);
+        v += __shfl_xor(v, 16);
+        v += __shfl_xor(v, 32);
+        if (q == 0 && b0 + li < B) value[b0 + li] = v + W.b_c2[0];
+    }
+    if (w != 0) return;
+
+    // logits of the tile: accumulator i of lane (li, q) is row 4 q + i, action li
+    f32x4 lg[1] = {splat(W.b_a2[arow])};
+    stream<1, H>(lg, wa, wpa, wpa, bp + li * SH + 8 * q);
+    const bool live_a = li < A;
+    u32 k0 = 0, k1 = 0;
+    if (mode == 0) {
+        k0 = key[0];
+        k1 = key[1];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int b = b0 + 4 * q + i;
+        const bool live = b < B;
+        const float x = lg[0][i];
+        if (logits && live && live_a) logits[(size_t)b * A + li] = x;
+        float sc = x;  // the score whose first argmax is the action
+        if (mode == 0) sc = x + gumbel_from_bits(threefry_bits(k0, k1, 0u, (u32)min(b, B - 1) * (u32)A + (u32)li));
+        sc = live_a ? sc : -INFINITY;
+        int idx = li;
+        float mx = live_a ? x : -INFINITY;
+#pragma unroll
+        for (int m = 1; m < 16; m <<= 1) {
+            const float os = __shfl_xor(sc, m);
+            const int oi = __shfl_xor(idx, m);
+            if (os > sc || (os == sc && oi < idx)) {
+                sc = os;
+                idx = oi;
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, m));
+        }
+        float sum = live_a ? expf(x - mx) : 0.0f;
+#pragma unroll
+        for (int m = 1; m < 16; m <<= 1) sum += __shfl_xor(sum, m);
+        const float xa = __shfl(x, (l & 48) | idx);
+        if (live && li == 0) {
+            action[b] = idx;
+            log_prob[b] = xa - mx - logf(sum);
+        }
+    }
+}
+
+int launch_status() {
+    const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? HFTLOB_OK : hftlob_fail(HFTLOB_ELAUNCH, hipGetErrorString(err));
+}
+
+bool size_ok(int n) { return n == 64 || n == 128 || n == 256; }
+bool misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+}  // namespace
+
+extern "C" int hftlob_policy_step(int B, int D, int FC, int H, int A, const hftlob_policy_weights* w, const float* obs,
+                                  const uint8_t* done, const float* h_in, float* h_out, int mode, const uint32_t* key,
+                                  int32_t* action, float* log_prob, float* value, float* logits, void* stream) {
+    if (B < 1) return hftlob_fail(HFTLOB_ESHAPE, "policy_step: B must be >= 1");
+    if (!size_ok(H)) return hftlob_fail(HFTLOB_ESHAPE, "policy_step: H must be 64, 128 or 256");
+    if (!size_ok(FC)) return hftlob_fail(HFTLOB_ESHAPE, "policy_step: FC must be 64, 128 or 256");
+    if (D < 1 || D > DMAX) return hftlob_fail(HFTLOB_ESHAPE, "policy_step: D must be in 1..64");
+    if (A < 1 || A > 16) return hftlob_fail(HFTLOB_ESHAPE, "policy_step: A must be in 1..16");
+    if (mode != 0 && mode != 1) return hftlob_fail(HFTLOB_EINVAL, "policy_step: mode must be 0 (sample) or 1 (argmax)");
+    if (!w) return hftlob_fail(HFTLOB_ENULL, "policy_step: w (the weight struct) is NULL");
+    if (!w->w_embed || !w->b_embed || !w->w_ih || !w->b_ih || !w->w_hh || !w->b_hh || !w->w_c1 || !w->b_c1 ||
+        !w->w_c2 || !w->b_c2 || !w->w_a1 || !w->b_a1 || !w->w_a2 || !w->b_a2)
+        return hftlob_fail(HFTLOB_ENULL, "policy_step: a pointer of the weight struct w is NULL");
+    if (!obs) return hftlob_fail(HFTLOB_ENULL, "policy_step: obs is NULL");
+    if (!done) return hftlob_fail(HFTLOB_ENULL, "policy_step: done is NULL");
+    if (!h_in) return hftlob_fail(HFTLOB_ENULL, "policy_step: h_in is NULL");
+    if (!h_out) return hftlob_fail(HFTLOB_ENULL, "policy_step: h_out is NULL");
+    if (mode == 0 && !key) return hftlob_fail(HFTLOB_ENULL, "policy_step: key is NULL (mode 0 samples from it)");
+    if (!action) return hftlob_fail(HFTLOB_ENULL, "policy_step: action is NULL");
+    if (!log_prob) return hftlob_fail(HFTLOB_ENULL, "policy_step: log_prob is NULL");
+    if (!value) return hftlob_fail(HFTLOB_ENULL, "policy_step: value is NULL");
+    if (misaligned(w->w_ih) || misaligned(w->w_hh) || misaligned(w->w_c1) || misaligned(w->w_a1) || misaligned(w->w_a2))
+        return hftlob_fail(HFTLOB_EINVAL, "policy_step: w_ih, w_hh, w_c1, w_a1 and w_a2 must be 16-byte aligned");
+    const dim3 grid((unsigned)((B + TILE - 1) / TILE));
+    hipStream_t s = (hipStream_t)stream;
+#define HFTLOB_POLICY_CASE(h, fc)                                                                                  \
+    if (H == h && FC == fc)                                                                                        \
+        k_policy_step<h, fc><<<grid, Shape<h, fc>::NT, 0, s>>>(B, D, A, *w, obs, done, h_in, h_out, mode, key, action, \
+                                                               log_prob, value, logits);
+    HFTLOB_POLICY_CASE(64, 64)
+    HFTLOB_POLICY_CASE(64, 128)
+    HFTLOB_POLICY_CASE(64, 256)
+    HFTLOB_POLICY_CASE(128, 64)
+    HFTLOB_POLICY_CASE(128, 128)
+    HFTLOB_POLICY_CASE(128, 256)
+    HFTLOB_POLICY_CASE(256, 64)
+    HFTLOB_POLICY_CASE(256, 128)
+    HFTLOB_POLICY_CASE(256, 256)
+#undef HFTLOB_POLICY_CASE
+    return launch_status();
+}

@@ -18,6 +18,12 @@ class LaunchInfo(C.Structure):
                 ("rows_alias", C.c_int32), ("lds_bytes", C.c_int32), ("tick_magic", C.c_uint32),
                 ("key_batch", C.c_int32)]
 
+class PolicyWeights(C.Structure):
+    """hftlob_policy_weights (include/hftlob.h): device pointers of one ActorCriticRNN's parameters."""
+    _fields_ = [(n, C.c_void_p) for n in ("w_embed", "b_embed", "w_ih", "b_ih", "w_hh", "b_hh", "w_c1", "b_c1",
+                                          "w_c2", "b_c2", "w_a1", "b_a1", "w_a2", "b_a2")]
+
+
 LIB_PATH = os.environ.get("HFTLOB_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhftlob.so")
 ABI_VERSION = 8
 EVAL_WORDS = 106  # HFTLOB_EVAL_WORDS: doubles per agent in hftlob_env_rollout_eval's stats (the table is in hftlob.h)
@@ -26,7 +32,8 @@ EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob
            "hftlob_env_step", "hftlob_env_step_sampled", "hftlob_env_rollout_sampled", "hftlob_rollout_prepare",
            "hftlob_env_rollout_actions", "hftlob_env_rollout_eval",
            "hftlob_env_lds_bytes", "hftlob_env_launch_info",
-           "hftlob_sample_actions", "hftlob_split_keys", "hftlob_gru_scan_fwd", "hftlob_gru_scan_bwd")
+           "hftlob_sample_actions", "hftlob_split_keys", "hftlob_gru_scan_fwd", "hftlob_gru_scan_bwd",
+           "hftlob_policy_step")
 
 _lib = None
 
@@ -80,6 +87,9 @@ def lib() -> C.CDLL:
     L.hftlob_gru_scan_fwd.restype = i32
     L.hftlob_gru_scan_bwd.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.hftlob_gru_scan_bwd.restype = i32
+    L.hftlob_policy_step.argtypes = [i32, i32, i32, i32, i32, C.POINTER(PolicyWeights), vp, vp, vp, vp, i32, vp,
+                                     vp, vp, vp, vp, vp]
+    L.hftlob_policy_step.restype = i32
     if L.hftlob_version() != ABI_VERSION:
         raise RuntimeError(f"libhftlob ABI {L.hftlob_version()} != {ABI_VERSION}")
     _lib = L

@@ -11,8 +11,12 @@ into per-agent accumulators instead of writing a trajectory.
   into counts, means and population standard deviations per agent type.
 * :func:`evaluate_fixed_actions` is the script's loop; ``python -m hftlob.evaluate`` prints its
   numbers as one JSON object.
+* :func:`evaluate_policy` is the same loop with the recurrent policies of a checkpoint
+  (``hftlob.train.ippo.load_policy``) in place of the fixed actions: one fused policy step per agent
+  type and one env step per step, reduced with :func:`reduce_steps`
+  (``python -m hftlob.evaluate --checkpoint PATH``).
 
-Checkpoint evaluation and plotting (the rest of baseline_eval/) are not covered.
+Plotting (the rest of baseline_eval/) is not covered.
 """
 from __future__ import annotations
 
@@ -196,13 +200,23 @@ def eval_keys(rng: torch.Tensor, n_envs: int, n_steps: int, partitionable: bool)
     per step ``rng, _ = split(rng)`` (the unused action sample) and ``rng, _rng = split(rng)``, then
     ``split(_rng, n_envs)`` for all the steps at once.  Returns (rng', keys [n_steps, n_envs, 2])."""
     from .env import split_keys
-    sub = []
+    rng, sub, _ = _key_chain(rng, n_steps, partitionable)
+    return rng, split_keys(torch.cat(sub).contiguous(), n_envs, partitionable)
+
+
+def _key_chain(rng: torch.Tensor, n_steps: int, partitionable: bool):
+    """The chain of :func:`eval_keys`: (rng', each step's ``_rng`` [1, 2], each step's action-sample
+    key [1, 2]: the second key of the step's first split, which a fixed-action run leaves unused)."""
+    from .env import split_keys
+    sub, act = [], []
     for _ in range(n_steps):
-        rng = split_keys(rng, 2, partitionable)[:, 0].contiguous()
+        first = split_keys(rng, 2, partitionable)
+        rng = first[:, 0].contiguous()
+        act.append(first[:, 1])
         pair = split_keys(rng, 2, partitionable)
         rng = pair[:, 0].contiguous()
         sub.append(pair[:, 1])
-    return rng, split_keys(torch.cat(sub).contiguous(), n_envs, partitionable)
+    return rng, sub, act
 
 
 def evaluate_fixed_actions(env, fixed_actions: Sequence, n_envs: int, n_steps: int, seed: int,
@@ -229,27 +243,107 @@ def evaluate_fixed_actions(env, fixed_actions: Sequence, n_envs: int, n_steps: i
     return EvalStats(stats, env.layout)
 
 
-def main(argv=None) -> int:
+def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: bool = True,
+                    chunk: int = 64) -> EvalStats:
+    """:func:`evaluate_fixed_actions` with recurrent policies in place of the fixed actions: ``nets``
+    holds one ``ActorCriticRNN`` per agent type (``hftlob.train.ippo.load_policy``).  The reset and
+    the env step keys are that function's chain unchanged; the key its chain leaves unused each step
+    (:func:`eval_keys`' "unused action sample") is the step's policy key, split once more per agent
+    type.  Each step is one fused ``policy_step`` per type (the argmax if ``greedy``, else a
+    ``jax.random.categorical`` sample) followed by ``env.step``; the carries start at zero and are
+    reset by each actor's done.  The rewards, raw info words and global dones of ``chunk`` steps are
+    kept and reduced with :func:`reduce_steps`, the stats carried from chunk to chunk.  The env
+    must be built with ``return_info=True``."""
+    from .env import split_keys
+    from .train.policy import GREEDY, SAMPLE, policy_step
+    if n_envs < 1 or n_steps < 1 or chunk < 1:
+        raise ValueError("n_envs, n_steps and chunk must be >= 1")
+    if not getattr(env, "return_info", False):
+        raise ValueError("evaluate_policy reduces the steps' info words: build the env with return_info=True")
+    counts = list(env.multi_agent_config.number_of_agents_per_type)
+    if len(nets) != len(counts):
+        raise ValueError(f"nets must hold one network per agent type ({len(counts)}), got {len(nets)}")
+    part = bool(env.cfg_c.prng_partitionable)
+    params, dev, E, L = env.default_params, env.device, n_envs, env.layout
+    mode = GREEDY if greedy else SAMPLE
+    rng = torch.tensor([[0, int(seed) & 0xFFFFFFFF]], dtype=torch.int64).to(torch.int32).to(dev)
+    pair = split_keys(rng, 2, part)
+    rng = pair[:, 0].contiguous()
+    obs, state = env.reset(split_keys(pair[:, 1].contiguous(), n_envs, part)[0], params)
+    n_act = [n * E for n in counts]
+    obs = [o.reshape(n, -1).contiguous() for o, n in zip(obs, n_act)]
+    done = [torch.zeros(n, dtype=torch.bool, device=dev) for n in n_act]
+    h = [torch.zeros(n, net.hidden, device=dev) for n, net in zip(n_act, nets)]
+    stats = None
+    for t0 in range(0, n_steps, chunk):
+        T = min(chunk, n_steps - t0)
+        rng, sub, act = _key_chain(rng, T, part)
+        keys = split_keys(torch.cat(sub).contiguous(), n_envs, part)                       # [T, E, 2]
+        pol = split_keys(torch.cat(act).contiguous(), len(nets), part)                     # [T, n_types, 2]
+        rew = [torch.empty((T, E, n), dtype=torch.float32, device=dev) for n in counts]
+        info = torch.empty((T, E, L.info_words), dtype=torch.int32, device=dev)
+        done_all = torch.empty((T, E), dtype=torch.bool, device=dev)
+        for t in range(T):
+            actions = []
+            for i, net in enumerate(nets):
+                a = policy_step(net, obs[i], done[i], h[i], mode, key=pol[t, i] if mode == SAMPLE else None)[1]
+                actions.append(a.view(E, counts[i]))
+            o, state, r, d, _ = env.step(keys[t], state, actions, params)
+            info[t].copy_(env.last_info_words)
+            done_all[t].copy_(d["__all__"])
+            for i, n in enumerate(n_act):
+                rew[i][t].copy_(r[i].reshape(E, counts[i]))
+                obs[i] = o[i].reshape(n, -1).contiguous()
+                done[i] = d["agents"][i].reshape(-1).contiguous()
+        stats = reduce_steps(rew, info, done_all, L, stats)
+    return EvalStats(stats, L)
+
+
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m hftlob.evaluate", description=__doc__.split("\n\n")[0])
     ap.add_argument("--env-config", required=True, help="a built-in config name, or the path of a config .json")
-    ap.add_argument("--fixed-actions", required=True,
-                    help="one action per agent type, comma-separated (the reference's FIXED_ACTIONS)")
+    what = ap.add_mutually_exclusive_group(required=True)
+    what.add_argument("--fixed-actions",
+                      help="one action per agent type, comma-separated (the reference's FIXED_ACTIONS)")
+    what.add_argument("--checkpoint", metavar="PATH",
+                      help="evaluate the policies of an IPPOTrainer checkpoint (python -m hftlob.train.ippo --save)")
+    ap.add_argument("--sample", action="store_true",
+                    help="with --checkpoint: sample the actions (jax.random.categorical) instead of the argmax")
     ap.add_argument("--envs", type=int, required=True)
     ap.add_argument("--steps", type=int, required=True)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--chunk", type=int, default=256, help="steps per launch")
+    ap.add_argument("--chunk", type=int, default=None,
+                    help="steps per launch (default 256), or with --checkpoint per reduction (default 64)")
     ap.add_argument("--data-msgs", type=int, default=400_000, help="length of the synthetic message day")
     ap.add_argument("--device", default="cuda:0")
+    return ap
+
+
+def main(argv=None) -> int:
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if args.sample and not args.checkpoint:
+        ap.error("--sample needs --checkpoint")
     from .config_io import builtin_config, load_config_from_file
     from .data.synthetic import generate_day
     from .env import MARLEnv
     cfg = load_config_from_file(args.env_config) if os.path.exists(args.env_config) else builtin_config(args.env_config)
     w = cfg.world_config
     day = generate_day(n_msgs=args.data_msgs, snap_every=w.n_data_msg_per_step * w.start_resolution)
+    if args.checkpoint:
+        from .train.ippo import load_policy
+        env = MARLEnv(None, cfg, data=day, device=args.device, return_info=True, persistent_outputs=True)
+        nets = load_policy(args.checkpoint, env, args.device)
+        ev = evaluate_policy(env, nets, args.envs, args.steps, args.seed, greedy=not args.sample,
+                             chunk=args.chunk or 64)
+        out = {"env_config": args.env_config, "checkpoint": args.checkpoint, "sample": bool(args.sample),
+               "envs": args.envs, "steps": args.steps, "seed": args.seed}
+        out.update(ev.summary())
+        print(json.dumps(out))
+        return 0
     env = MARLEnv(None, cfg, data=day, device=args.device, return_info=False, persistent_outputs=True)
     actions = [int(x) for x in args.fixed_actions.split(",")]
-    ev = evaluate_fixed_actions(env, actions, args.envs, args.steps, args.seed, args.chunk)
+    ev = evaluate_fixed_actions(env, actions, args.envs, args.steps, args.seed, args.chunk or 256)
     out = {"env_config": args.env_config, "fixed_actions": actions, "envs": args.envs, "steps": args.steps,
            "seed": args.seed}
     out.update(ev.summary())

@@ -28,7 +28,10 @@ kernels, and replaying them as one graph removes their launch cost.
 
 Differences that are not semantics of the env: action sampling and parameter
 initialisation draw from torch's generator, not JAX's threefry, and the network
-runs through torch (rocBLAS GEMMs) rather than XLA.
+runs through torch (rocBLAS GEMMs) rather than XLA.  With ``FUSED_POLICY`` the rollout's
+policy step is one HIP launch per agent type and step (``train.policy.policy_step``) and its
+samples are ``jax.random.categorical`` draws from a carried threefry key, so nothing inside the
+rollout reads torch's generator.
 """
 from __future__ import annotations
 
@@ -43,6 +46,7 @@ import torch.nn.functional as F
 
 from ..env import MARLEnv, split_keys
 from .gru import SUPPORTED_HIDDEN, gru_scan, gru_scan_supported
+from .policy import MAX_ACTIONS, MAX_OBS_DIM, SAMPLE, policy_step, policy_step_supported
 
 
 def _per_type(v, n: int) -> list:
@@ -57,7 +61,7 @@ def default_config(**kw) -> Dict:
          "TOTAL_TIMESTEPS": 5e8, "UPDATE_EPOCHS": 4, "NUM_MINIBATCHES": 4, "GAMMA": [0.999999999, 0.999],
          "GAE_LAMBDA": [0.85, 0.9], "CLIP_EPS": 0.2, "ENT_COEF": [0.01, 0.01], "VF_COEF": [0.5, 0.5],
          "MAX_GRAD_NORM": [0.5, 0.5], "ANNEAL_LR": [True, True], "NUM_AGENTS_PER_TYPE": [1, 1], "SEED": 2,
-         "CUDA_GRAPHS": True, "FUSED_GRU": False}
+         "CUDA_GRAPHS": True, "FUSED_GRU": False, "FUSED_POLICY": False}
     c.update(kw)
     return c
 
@@ -211,6 +215,18 @@ class IPPOTrainer:
                                  f"got {c['GRU_HIDDEN_DIM']}")
             for n in self.nets:
                 n.fused = self.device.type == "cuda"
+        # FUSED_POLICY: the rollout's policy step, sample and log-prob as one HIP launch per agent type
+        # and step (train.policy.policy_step; GPU only, and there is no other path behind the switch)
+        self.fused_policy = bool(c.get("FUSED_POLICY", False))
+        if self.fused_policy:
+            if self.device.type != "cuda":
+                raise ValueError(f"FUSED_POLICY needs a GPU device, got {self.device}")
+            for i, n in enumerate(self.nets):
+                D, A = n.embed.in_features, n.actor2.out_features
+                if not policy_step_supported(D, c["FC_DIM_SIZE"], c["GRU_HIDDEN_DIM"], A):
+                    raise ValueError(f"FUSED_POLICY needs GRU_HIDDEN_DIM and FC_DIM_SIZE in {list(SUPPORTED_HIDDEN)}, "
+                                     f"an observation size <= {MAX_OBS_DIM} and <= {MAX_ACTIONS} actions, got "
+                                     f"{c['GRU_HIDDEN_DIM']}, {c['FC_DIM_SIZE']}, {D} and {A} (agent type {i})")
         # HIP-graph minibatch steps: single process on the GPU (the grad all-reduce stays eager)
         self.graphs = bool(c.get("CUDA_GRAPHS", False)) and self.device.type == "cuda" and world == 1
         if self.graphs:  # capturable Adam: step counter and lr live on the device
@@ -235,6 +251,11 @@ class IPPOTrainer:
         self.rng = (k[0] if world == 1 else self._split(k[0:1].contiguous(), world)[0][rank]).clone()
         reset_keys = self._split(k[1:2].contiguous(), n_global)[0][rank * self.E:(rank + 1) * self.E].contiguous()
         self.reset_keys = reset_keys
+        if self.fused_policy:
+            # the sample keys' own chain, from a key no other chain uses (words "pol", SEED), so that
+            # rng, the reset keys and every env step key are what they are without the switch
+            pm = torch.tensor([[0x706F6C, c["SEED"]]], dtype=torch.int32, device=self.device)
+            self.pol_rng = self._split(pm, world + 1)[0][rank + 1].clone()
         obs, self.state = env.reset(reset_keys, self.params)
         self.last_obs = [o.reshape(n, -1).clone() for o, n in zip(obs, self.n_actors)]
         self.last_done = [torch.zeros(n, dtype=torch.bool, device=self.device) for n in self.n_actors]
@@ -292,6 +313,13 @@ class IPPOTrainer:
                 b = self.buf[i]
                 b.obs[t].copy_(self.last_obs[i])
                 b.done[t].copy_(self.last_done[i])
+                if self.fused_policy:  # pol_rng, sub = split(pol_rng); one launch: carry in place, outputs into the buffers
+                    k = self._split(self.pol_rng[None], 2)[0]
+                    self.pol_rng.copy_(k[0])
+                    policy_step(net, self.last_obs[i], self.last_done[i], self.h[i], SAMPLE, key=k[1],
+                                out=(b.action[t], b.log_prob[t], b.value[t]))
+                    actions.append(b.action[t].view(self.E, self.n_agents[i]))
+                    continue
                 h, logits, v = net.step(self.h[i], self.last_obs[i], self.last_done[i])
                 self.h[i].copy_(h)
                 probs = torch.softmax(logits, -1)
@@ -394,6 +422,66 @@ class IPPOTrainer:
             metrics["avg_reward"].append(b.reward.mean())
         return metrics
 
+    # ------------------------------------------------------------------ checkpoints
+    def save_checkpoint(self, path: str) -> None:
+        """torch.save of every net's state_dict, the optimisers' states, opt_count, the config and
+        the env config (``env.config_name`` where the env carries one, else its dict)."""
+        from dataclasses import asdict, is_dataclass
+        mc = getattr(self.env, "multi_agent_config", None)
+        env_cfg = getattr(self.env, "config_name", None) or (asdict(mc) if is_dataclass(mc) else None)
+        torch.save({"format": CHECKPOINT_FORMAT, "nets": [n.state_dict() for n in self.nets],
+                    "opts": [o.state_dict() for o in self.opts], "opt_count": list(self.opt_count),
+                    "config": dict(self.c), "env_config": env_cfg,
+                    "shapes": [(n.embed.in_features, n.actor2.out_features) for n in self.nets]}, path)
+
+    def load_checkpoint(self, path: str) -> None:
+        """Restores what ``save_checkpoint`` wrote into this trainer (same env and sizes).  The
+        parameters are copied in place (a captured rollout stays valid); the optimisers get new
+        state tensors, so the minibatch graphs are captured again at the next update."""
+        ck = _read_checkpoint(path)
+        if len(ck["nets"]) != self.n_types:
+            raise ValueError(f"{path}: {len(ck['nets'])} agent types, this trainer has {self.n_types}")
+        for net, opt, sd, od in zip(self.nets, self.opts, ck["nets"], ck["opts"]):
+            net.load_state_dict(sd)
+            for g in od["param_groups"]:   # capturable Adam keeps lr on the device, the eager one as a float
+                g["capturable"] = self.graphs
+                g["lr"] = torch.tensor(float(g["lr"]), device=self.device) if self.graphs else float(g["lr"])
+            opt.load_state_dict(od)
+        self.opt_count = list(ck["opt_count"])
+        for st in getattr(self, "_st", []):
+            if st is not None:
+                st.update(warm=0, graph=None, out=None)
+
+
+CHECKPOINT_FORMAT = "hftlob-ippo-1"
+
+
+def _read_checkpoint(path: str) -> Dict:
+    # onto the CPU: load_state_dict copies into the parameters and moves the optimiser state itself
+    ck = torch.load(path, map_location="cpu", weights_only=False)
+    if not isinstance(ck, dict) or ck.get("format") != CHECKPOINT_FORMAT:
+        raise ValueError(f"{path} is not an IPPOTrainer checkpoint ({CHECKPOINT_FORMAT})")
+    return ck
+
+
+def load_policy(path: str, env=None, device=None) -> List[ActorCriticRNN]:
+    """The nets of a checkpoint alone (eval mode, on ``device``, default the env's), one per agent
+    type; with ``env`` given their sizes are checked against its observation and action spaces."""
+    device = torch.device(device or (env.device if env is not None else "cpu"))
+    ck = _read_checkpoint(path)
+    c = ck["config"]
+    nets = []
+    for i, (sd, (D, A)) in enumerate(zip(ck["nets"], ck["shapes"])):
+        if env is not None and (env.observation_spaces[i].shape[0] != D or env.action_spaces[i].n != A):
+            raise ValueError(f"{path}: agent type {i} has obs {D} / {A} actions, the env "
+                             f"{env.observation_spaces[i].shape[0]} / {env.action_spaces[i].n}")
+        net = ActorCriticRNN(D, A, c["FC_DIM_SIZE"], c["GRU_HIDDEN_DIM"]).to(device)
+        net.load_state_dict(sd)
+        nets.append(net.eval())
+    if env is not None and len(nets) != len(env.action_spaces):
+        raise ValueError(f"{path}: {len(nets)} agent types, the env has {len(env.action_spaces)}")
+    return nets
+
 
 def train(env: MARLEnv, config: Dict, n_updates: Optional[int] = None, dist=None, log=print):
     """Runs ``n_updates`` (default NUM_UPDATES) updates; returns (trainer, env-steps/s over the run)."""
@@ -424,6 +512,9 @@ def main(argv=None) -> None:
     ap.add_argument("--updates", type=int, default=2)
     ap.add_argument("--envs", type=int, default=None)
     ap.add_argument("--fused-gru", action="store_true", help="the PPO update's GRU scan as the fused HIP operators")
+    ap.add_argument("--fused-policy", action="store_true",
+                    help="the rollout's policy step, sample and log-prob as one fused HIP launch")
+    ap.add_argument("--save", default=None, metavar="PATH", help="write a checkpoint here after the last update")
     ap.add_argument("--data", default=None, help="'lobster' to load world_config.dataPath (else synthetic)")
     a = ap.parse_args(argv)
     c = default_config()
@@ -434,10 +525,16 @@ def main(argv=None) -> None:
         c["NUM_ENVS"] = a.envs
     if a.fused_gru:
         c["FUSED_GRU"] = True
+    if a.fused_policy:
+        c["FUSED_POLICY"] = True
     cfg = (load_config_from_file(a.env_config) if a.env_config.endswith((".json", ".yaml"))
            else builtin_config(a.env_config))
     env = MARLEnv(None, cfg, data=a.data, return_info=False, persistent_outputs=True)
-    _, sps = train(env, c, a.updates, log=lambda m: print(json.dumps(m)))
+    if not a.env_config.endswith((".json", ".yaml")):
+        env.config_name = a.env_config   # what a checkpoint records instead of the config's dict
+    tr, sps = train(env, c, a.updates, log=lambda m: print(json.dumps(m)))
+    if a.save:
+        tr.save_checkpoint(a.save)
     print(json.dumps({"env_steps_per_s_incl_learner": sps, "num_envs": c["NUM_ENVS"], "num_steps": c["NUM_STEPS"]}))
 
 

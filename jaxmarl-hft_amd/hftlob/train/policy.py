@@ -1,0 +1,198 @@
+"""One ``ActorCriticRNN`` step for a batch of actors (ippo_rnn_JAXMARL.py:53-78, 183-256) with the
+rollout's sample and log-probability, as one engine operator (``hftlob_policy_step``,
+include/hftlob.h) and its restatement.
+
+``policy_step_reference`` restates the operator in torch, in whatever float type it is given: it
+is the spec of the kernel and what the tests compare against.  ``policy_step`` is the fused
+path: one HIP launch, used by the trainer's rollout (``FUSED_POLICY``) and by
+``hftlob.evaluate.evaluate_policy``.
+
+Sampling (mode 0) is ``jax.random.categorical(key, logits)``: the first argmax of
+``logits + g`` with ``g = jax.random.gumbel(key, (B, A))`` under the partitionable threefry
+(``gumbel_noise``; the legacy threefry is not built).  Mode 1 is the first argmax of the logits.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict
+
+import numpy as np
+import torch
+
+from .. import _lib
+
+SUPPORTED_HIDDEN = (64, 128, 256)   # GRU_HIDDEN_DIM and FC_DIM_SIZE of the kernel's instantiations (csrc/policy_step.hip)
+MAX_OBS_DIM = 64
+MAX_ACTIONS = 16
+SAMPLE, GREEDY = 0, 1               # the operator's modes
+
+WEIGHT_NAMES = ("w_embed", "b_embed", "w_ih", "b_ih", "w_hh", "b_hh", "w_c1", "b_c1", "w_c2", "b_c2",
+                "w_a1", "b_a1", "w_a2", "b_a2")
+
+
+def policy_step_supported(D: int, FC: int, H: int, A: int) -> bool:
+    """Whether the fused step has a kernel for these sizes (no GPU needed to ask)."""
+    return (int(FC) in SUPPORTED_HIDDEN and int(H) in SUPPORTED_HIDDEN and 1 <= int(D) <= MAX_OBS_DIM
+            and 1 <= int(A) <= MAX_ACTIONS)
+
+
+def net_weights(net) -> Dict[str, torch.Tensor]:
+    """The parameters of an ``ActorCriticRNN`` under the names of ``hftlob_policy_weights`` (the
+    parameters themselves, not copies); a dict of those names is returned as it is."""
+    if isinstance(net, dict):
+        return net
+    return {"w_embed": net.embed.weight, "b_embed": net.embed.bias,
+            "w_ih": net.gru.weight_ih, "b_ih": net.gru.bias_ih, "w_hh": net.gru.weight_hh, "b_hh": net.gru.bias_hh,
+            "w_c1": net.critic1.weight, "b_c1": net.critic1.bias, "w_c2": net.critic2.weight, "b_c2": net.critic2.bias,
+            "w_a1": net.actor1.weight, "b_a1": net.actor1.bias, "w_a2": net.actor2.weight, "b_a2": net.actor2.bias}
+
+
+# ------------------------------------------------------------------ the noise, on the CPU
+def threefry2x32(k0: int, k1: int, x0: np.ndarray, x1: np.ndarray):
+    """threefry2x32 with 20 rounds on uint32 arrays of counters, as JAX runs it."""
+    with np.errstate(over="ignore"):
+        ks = [np.uint32(k0), np.uint32(k1), np.uint32(k0) ^ np.uint32(k1) ^ np.uint32(0x1BD11BDA)]
+        x0 = (np.asarray(x0, dtype=np.uint32) + ks[0]).astype(np.uint32)
+        x1 = (np.asarray(x1, dtype=np.uint32) + ks[1]).astype(np.uint32)
+        rots = ((13, 15, 26, 6), (17, 29, 16, 24))
+        for i in range(1, 6):
+            for r in rots[(i - 1) % 2]:
+                x0 = (x0 + x1).astype(np.uint32)
+                x1 = ((x1 << np.uint32(r)) | (x1 >> np.uint32(32 - r))) ^ x0
+            x0 = (x0 + ks[i % 3]).astype(np.uint32)
+            x1 = (x1 + ks[(i + 1) % 3] + np.uint32(i)).astype(np.uint32)
+    return x0, x1
+
+
+def _key_words(key):
+    if isinstance(key, torch.Tensor):
+        key = key.detach().cpu().numpy()
+    k = np.asarray(key).reshape(-1)
+    if k.size != 2:
+        raise ValueError("a key is two 32-bit words")
+    return int(k[0]) & 0xFFFFFFFF, int(k[1]) & 0xFFFFFFFF
+
+
+def random_bits(key, n: int) -> np.ndarray:
+    """jax random_bits(key, 32, (n,)) under the partitionable threefry: uint32 [n], word i is
+    y0 ^ y1 of threefry2x32(key, (0, i))."""
+    k0, k1 = _key_words(key)
+    y0, y1 = threefry2x32(k0, k1, np.zeros(n, dtype=np.uint32), np.arange(n, dtype=np.uint32))
+    return y0 ^ y1
+
+
+def gumbel_from_bits(bits) -> np.ndarray:
+    """jax.random.gumbel's float32 draw from random words: f = bitcast((bits >> 9) | 0x3f800000) - 1,
+    u = max(tiny, f (1 - tiny) + tiny), g = -log(-log(u)), all in float32."""
+    bits = np.asarray(bits, dtype=np.uint32)
+    tiny = np.finfo(np.float32).tiny
+    f = ((bits >> np.uint32(9)) | np.uint32(0x3F800000)).view(np.float32) - np.float32(1.0)
+    u = np.maximum(tiny, f * (np.float32(1.0) - tiny) + tiny).astype(np.float32)
+    return (-np.log(-np.log(u))).astype(np.float32)
+
+
+def gumbel_noise(key, B: int, A: int) -> torch.Tensor:
+    """jax.random.gumbel(key, (B, A)) under the partitionable threefry: float32 [B, A] on the CPU
+    (element (b, a) is drawn from counter (0, b A + a))."""
+    return torch.from_numpy(gumbel_from_bits(random_bits(key, B * A)).reshape(B, A))
+
+
+# ------------------------------------------------------------------ the spec
+def policy_step_reference(net_or_weights, obs, done, h, mode: int, key=None, gumbel=None):
+    """hftlob_policy_step in torch, in the float type of ``obs`` (the weights are converted to
+    it): returns (h [B, H], logits [B, A], value [B], action int64 [B], log_prob [B]).  Mode 0
+    adds ``gumbel`` [B, A] to the logits before the argmax, or ``gumbel_noise(key, B, A)``."""
+    if mode not in (SAMPLE, GREEDY):
+        raise ValueError("mode must be 0 (sample) or 1 (argmax)")
+    dt, dev = obs.dtype, obs.device
+    W = {k: v.detach().to(device=dev, dtype=dt) for k, v in net_weights(net_or_weights).items()}
+    h = h.to(dt)
+    hp = torch.where(done.bool()[:, None], torch.zeros_like(h), h)
+    x = torch.relu(obs @ W["w_embed"].t() + W["b_embed"])
+    ir, iz, i_n = (x @ W["w_ih"].t() + W["b_ih"]).chunk(3, -1)
+    hr, hz, hn = (hp @ W["w_hh"].t() + W["b_hh"]).chunk(3, -1)
+    r = torch.sigmoid(ir + hr)
+    z = torch.sigmoid(iz + hz)
+    n = torch.tanh(i_n + r * hn)
+    hnew = (1.0 - z) * n + z * hp
+    value = (torch.relu(hnew @ W["w_c1"].t() + W["b_c1"]) @ W["w_c2"].t() + W["b_c2"]).squeeze(-1)
+    logits = torch.relu(hnew @ W["w_a1"].t() + W["b_a1"]) @ W["w_a2"].t() + W["b_a2"]
+    score = logits
+    if mode == SAMPLE:
+        if gumbel is None:
+            if key is None:
+                raise ValueError("mode 0 needs key or gumbel")
+            gumbel = gumbel_noise(key, logits.shape[0], logits.shape[1])
+        score = logits + gumbel.to(device=dev, dtype=dt)
+    # the first argmax: the smallest index among the maxima
+    top = score.max(-1, keepdim=True).values
+    A = logits.shape[-1]
+    action = torch.where(score == top, torch.arange(A, device=dev), torch.full((), A, device=dev)).min(-1).values
+    mx = logits.max(-1, keepdim=True).values
+    logp = logits - mx - torch.log(torch.exp(logits - mx).sum(-1, keepdim=True))
+    return hnew, logits, value, action, logp.gather(-1, action[:, None]).squeeze(-1)
+
+
+# ------------------------------------------------------------------ the fused path
+def _weights_struct(W: Dict[str, torch.Tensor], D: int, FC: int, H: int, A: int) -> _lib.PolicyWeights:
+    shapes = {"w_embed": (FC, D), "b_embed": (FC,), "w_ih": (3 * H, FC), "b_ih": (3 * H,), "w_hh": (3 * H, H),
+              "b_hh": (3 * H,), "w_c1": (FC, H), "b_c1": (FC,), "w_c2": (1, FC), "b_c2": (1,), "w_a1": (H, H),
+              "b_a1": (H,), "w_a2": (A, H), "b_a2": (A,)}
+    s = _lib.PolicyWeights()
+    for name in WEIGHT_NAMES:
+        t = W[name]
+        if tuple(t.shape) != shapes[name] or t.dtype != torch.float32:
+            raise ValueError(f"policy_step: {name} must be float32 {list(shapes[name])}, got {t.dtype} {list(t.shape)}")
+        setattr(s, name, _lib.ptr(t.detach()))   # (a CPU or non-contiguous tensor raises here)
+    return s
+
+
+def policy_step(net, obs, done, h, mode: int, key=None, out=None, h_out=None, logits: bool = False):
+    """hftlob_policy_step on device tensors: one launch on torch's current stream.
+
+    net: an ``ActorCriticRNN`` (or a dict of its parameters by ``WEIGHT_NAMES``); the struct is
+    built from the parameters' ``data_ptr()``s, which an in-place optimiser keeps valid across the
+    replays of a captured graph.  obs float32 [B, D]; done bool / uint8 [B]; h float32 [B, H].
+    mode 0 samples with ``key`` (uint32 / int32 [2] on the device), mode 1 takes the argmax.
+    out: ``(action int32 [B], log_prob float32 [B], value float32 [B])`` to write into (for example
+    rows of the rollout buffers); None allocates them.  h_out: where the new carry goes; None
+    updates ``h`` in place.  Returns ``(h_out, action, log_prob, value, logits or None)``."""
+    W = net_weights(net)
+    if obs.dim() != 2 or h.dim() != 2:
+        raise ValueError("policy_step: obs must be [B, D] and h [B, H]")
+    B, D = obs.shape
+    H = h.shape[1]
+    FC, A = W["w_embed"].shape[0], W["w_a2"].shape[0]
+    if not policy_step_supported(D, FC, H, A):
+        raise ValueError(f"policy_step needs GRU_HIDDEN_DIM and FC_DIM_SIZE in {list(SUPPORTED_HIDDEN)}, an obs size "
+                         f"in 1..{MAX_OBS_DIM} and 1..{MAX_ACTIONS} actions, got H {H}, FC {FC}, D {D}, A {A}")
+    if mode not in (SAMPLE, GREEDY):
+        raise ValueError("policy_step: mode must be 0 (sample) or 1 (argmax)")
+    dev = obs.device
+    if done.dtype == torch.bool:
+        done = done.view(torch.uint8)
+    h_out = h if h_out is None else h_out
+    if out is None:
+        out = (torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.float32, device=dev),
+               torch.empty(B, dtype=torch.float32, device=dev))
+    action, log_prob, value = out
+    lg = torch.empty((B, A), dtype=torch.float32, device=dev) if logits else None
+    for name, t, shape, dt in (("obs", obs, (B, D), torch.float32), ("done", done, (B,), torch.uint8),
+                               ("h", h, (B, H), torch.float32), ("h_out", h_out, (B, H), torch.float32),
+                               ("action", action, (B,), torch.int32), ("log_prob", log_prob, (B,), torch.float32),
+                               ("value", value, (B,), torch.float32)):
+        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev:
+            raise ValueError(f"policy_step: {name} must be {dt} {list(shape)} on {dev}, got {t.dtype} "
+                             f"{list(t.shape)} on {t.device}")
+    kp = None
+    if mode == SAMPLE:
+        if key is None or key.dtype not in (torch.int32, torch.uint32) or key.numel() != 2 or key.device != dev:
+            raise ValueError(f"policy_step: mode 0 needs key, a uint32/int32 tensor of 2 words on {dev}")
+        kp = _lib.ptr(key)
+    ws = _weights_struct(W, D, FC, H, A)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().hftlob_policy_step(B, D, FC, H, A, C.byref(ws), _lib.ptr(obs), _lib.ptr(done),
+                                                 _lib.ptr(h), _lib.ptr(h_out), int(mode), kp, _lib.ptr(action),
+                                                 _lib.ptr(log_prob), _lib.ptr(value), _lib.ptr(lg),
+                                                 _lib.stream_ptr(device=dev)))
+    return h_out, action, log_prob, value, lg
