@@ -444,6 +444,23 @@ typedef struct hftlob_launch_info {
 } hftlob_launch_info;
 int hftlob_env_launch_info(const hftlob_env_cfg* cfg /*[host]*/, hftlob_launch_info* out /*[host]*/);
 
+/* Baked configs.  The library holds the env configs the package ships (the JSON files of hftlob/configs, packed
+ * by hftlob.layout.pack_env_cfg) as compile-time constants, and for some of them an instantiation
+ * of hftlob_env_rollout_sampled's persistent kernel (n_slices = 0) that reads no config word at run
+ * time: today the ids 0 (2_player_fq_fqc) and 1 (3_player_fq_fqc_dir).  A launch takes it only when
+ * the caller's config equals the baked one in every word but n_windows and n_data_rows (the day's;
+ * they stay run-time words) and tick_magic (the library's own); any difference, a tick_size other
+ * than the builtin data's included, takes the general kernel.  The results are the same bit for bit
+ * either way, and hftlob_env_launch_info describes both (the variant is the same).  It replaces
+ * what jax.jit does for the reference, whose config is static Python data folded by XLA.
+ *
+ * hftlob_env_baked_id: the id (index in file-name order of the builtin configs) of the baked config
+ * `cfg` equals, or -1: no such config, an invalid cfg, or the switch below is off (host-only).
+ * hftlob_set_baked: process-wide switch, default on; on = 0 makes every launch take the general
+ * kernels (A/B runs and tests).  Returns the previous setting. */
+int hftlob_env_baked_id(const hftlob_env_cfg* cfg /*[host]*/);
+int hftlob_set_baked(int on);
+
 /* Speed_test action sampling (Speed_test.py:166-177, gymnax Discrete.sample):
  * for env e with step key k_e,
  * sub = split(k_e, n_types); per type t, agent i:

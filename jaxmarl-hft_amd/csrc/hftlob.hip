@@ -28,6 +28,9 @@
 
 #include "../../include/hftlob.h"
 #include "hftlob_internal.h"
+// the env configs the package ships, as compile-time constants (tools/gen_baked_cfg.py)
+#define HFTLOB_BAKED_QUAL static
+#include "baked_cfgs.inc"
 
 typedef int32_t i32;
 typedef uint32_t u32;
@@ -1869,17 +1872,38 @@ DEV void write_obs(const hftlob_env_cfg& c, const hftlob_agent_type_cfg& tc, con
     if (l < c.obs_stride) static_cast<float*>(dst)[l] = v;
 }
 
+// --------------------------------------------------------- baked configs
+// BAKED >= 0: the env config is the compile-time constant hftlob_baked_cfg_<BAKED> (baked_cfgs.inc)
+// apart from its run-time words (n_windows, n_data_rows: the day's); -1: the caller's struct.  A
+// baked step body reads no config word from memory, folds every branch on one and holds only the
+// agent / reward variants its config names; its loops over the types and their agents unroll fully
+// (their UNR count), so that c.types[t] is never indexed at run time.
+static_assert(HFTLOB_N_BAKED == 4, "baked_cfg names the table's entries one by one");
+template <int BAKED> DEV const hftlob_env_cfg& baked_cfg(const hftlob_env_cfg& rt) {
+    static_assert(BAKED >= -1 && BAKED < HFTLOB_N_BAKED, "no such baked config");
+    if constexpr (BAKED == 0) return hftlob_baked_cfg_0;
+    else if constexpr (BAKED == 1) return hftlob_baked_cfg_1;
+    else if constexpr (BAKED == 2) return hftlob_baked_cfg_2;
+    else if constexpr (BAKED == 3) return hftlob_baked_cfg_3;
+    else return rt;
+}
+// (unroll count of the loops over types / agents: all of them when baked, none otherwise)
+template <int BAKED> constexpr int baked_unroll() { return BAKED >= 0 ? HFTLOB_MAX_AGENTS : 1; }
+
 // ----------------------------------------- reset (MARLEnv.reset_env) device
 // marl_env.py:129-207; BaseLOBEnv.reset_env base_env.py:218-234; agents
 // mm_env.py:417-459, exec_env.py:209-266.  Writes the whole record + obs.
-template <int S>
-DEV void env_reset_dev(const hftlob_env_cfg& c, Key key, const i32* __restrict__ init_states, i32* __restrict__ rec,
+// BAKED, c_rt: as in env_step_dev (c_rt gives the day's window count, which no baked config holds).
+template <int S, int BAKED = -1>
+DEV void env_reset_dev(const hftlob_env_cfg& c_rt, Key key, const i32* __restrict__ init_states, i32* __restrict__ rec,
                        float* __restrict__ obs, const Valid<S>& VS, const Valid<S>& VT, bool ftime) {
+    const hftlob_env_cfg& c = baked_cfg<BAKED>(c_rt);
+    constexpr int UNR = baked_unroll<BAKED>();
     const bool part = c.prng_partitionable;
     const int nTy = c.n_types, l = lane_id();
     Key wk = split_key(key, nTy + 1, nTy, part);
-    i32 idx = c.window_selector == -1 ? randint(wk, 0, c.n_windows, part) : c.window_selector;
-    idx = imin_(imax_(idx, 0), c.n_windows - 1);
+    i32 idx = c.window_selector == -1 ? randint(wk, 0, c_rt.n_windows, part) : c.window_selector;
+    idx = imin_(imax_(idx, 0), c_rt.n_windows - 1);
     const i32* src = init_states + (size_t)idx * c.init_rec_words;
     // copy the LoadedEnvState prefix (asks, bids, trades, 6 scalars), 16B vectors
     for (int w = l * 4; w < c.init_rec_words; w += 256) {
@@ -1912,16 +1936,19 @@ DEV void env_reset_dev(const hftlob_env_cfg& c, Key key, const i32* __restrict__
     wv.t0 = wv.it0 = t0; wv.t1 = wv.it1 = t1; wv.dt = 0.0f;  // world time = init_time, delta_time 0
     // zero the record's padding words (after the world block, after the agents)
     int agents_end = c.off_agents;
+#pragma unroll UNR
     for (int t = 0; t < nTy; ++t) agents_end += c.types[t].n_agents * agent_words(c.types[t]);
     for (int w = c.off_world + 5 + l; w < c.off_agents; w += 64) rec[w] = 0;
     for (int w = agents_end + l; w < c.rec_words; w += 64) rec[w] = 0;
     i32* st = rec + c.off_agents;
     int ag = 0;
+#pragma unroll UNR
     for (int t = 0; t < nTy; ++t) {
         const hftlob_agent_type_cfg& tc = c.types[t];
         i32 sell = tc.task == HFTLOB_TASK_SELL ? 1 : 0;
         if (tc.kind == HFTLOB_AGENT_EXE && tc.task == HFTLOB_TASK_RANDOM)
             sell = randint(split_key(key, nTy + 1, t, part), 0, 2, part);
+#pragma unroll UNR
         for (int i = 0; i < tc.n_agents; ++i, ++ag) {
             i32 s[13];
             if (tc.kind == HFTLOB_AGENT_MM) {
@@ -3338,7 +3365,9 @@ DEV void tally_store(double* row, const TallyLane& t, float rew, const i32 (&iw)
 }
 // NFIX > 0: nOrders == nTrades == NFIX known at compile time (the reference's
 // 100/100 default), which folds the slot-validity masks away.
-template <int S, int NFIX, bool RC, bool RA = false, bool QUIET = false, int PK = -1, bool TALLY = false>
+template <int S, int NFIX, bool RC, bool RA = false, bool QUIET = false, int PK = -1, bool TALLY = false,
+          int BAKED = -1>
+// BAKED: the config is a baked one (baked_cfg above); c_rt then gives the run-time words only.
 // RC: cancel_mode 2/3 (the random cancel fallback of the engine).  RA: the agent rows live in the
 // trade log (lds_map).  QUIET: a step whose outputs are never emitted (emit = false at compile
 // time: k_env_rollout's per_step = 0 steps before the last, whose copy of the step body then holds
@@ -3361,7 +3390,7 @@ template <int S, int NFIX, bool RC, bool RA = false, bool QUIET = false, int PK 
 // state), and each step's outputs would be overwritten by the next.  Then the observations, the
 // reward values (not the PnL / cash / inventory / execution statistics the agent states carry),
 // the dones and the output stores are skipped; the state is bit-identical either way.
-DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u32* __restrict__ keys, bool master,
+DEV bool env_step_dev(const hftlob_env_cfg& c_rt, int key_n, int ek, int e, const u32* __restrict__ keys, bool master,
                       Key& mk,
                       i32* __restrict__ actions_io, const i32* __restrict__ msg_data,
                       const i32* __restrict__ init_states, i32* __restrict__ state, float* __restrict__ obs_out,
@@ -3370,6 +3399,8 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
                       i32* __restrict__ debug_out, i32* lds, bool resident, bool keep, u32& fl_carry,
                       const i32* pre_keys = nullptr, bool emit_rt = true, double* __restrict__ stats = nullptr,
                       int act_e = -1) {
+    const hftlob_env_cfg& c = baked_cfg<BAKED>(c_rt);
+    constexpr int UNR = baked_unroll<BAKED>();
     const bool emit = !QUIET && emit_rt;
     const bool vals = TALLY || emit;  // the reward values are wanted (the observations: emit)
     STAMP(t_start);
@@ -3418,6 +3449,7 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
     const float wmid = bitf(Wr[W_MID]);
     const i32 old_last_ba = rec[c.off_best_asks + (M - 1) * 2], old_last_bb = rec[c.off_best_bids + (M - 1) * 2];
     bool excl_any = false, excl_cfg = false;
+#pragma unroll UNR
     for (int t = 0; t < c.n_types; ++t) {
         const bool ex = c.types[t].kind == HFTLOB_AGENT_MM && c.types[t].exclude_extreme_spreads;
         excl_cfg |= ex;
@@ -3441,7 +3473,7 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
     // the data window (BaseLOBEnv.get_data_messages, base_env.py:339-369); its
     // first chunk is fetched now, ahead of the agent phase
     i32 dstart = wadd(start_index, wmul(D, step));
-    dstart = imax_(0, imin_(dstart, c.n_data_rows - D));  // dynamic_slice clamping
+    dstart = imax_(0, imin_(dstart, c_rt.n_data_rows - D));  // dynamic_slice clamping
     // fixed_time: rows at or after init_time[0] + episode_time keep only their time (base_env.py:358-367)
     const bool ftime = NFIX == 0 && c.ep_type == 1;  // the 100/100 kernel is launched for fixed_steps only
     const i32 t_end = wadd(ld_t0, c.episode_time);
@@ -3476,8 +3508,10 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
     {
         int ag = 0, arow = C, crow = 0, aw = 0;
         const i32* st = rec + c.off_agents;
+#pragma unroll UNR
         for (int t = 0; t < c.n_types; ++t) {
             const hftlob_agent_type_cfg& tc = c.types[t];
+#pragma unroll UNR
             for (int i = 0; i < tc.n_agents; ++i, ++ag) {
                 const i32 tid = wsub(tc.trader_id0, i);
                 const int w = tc.action_width;
@@ -3821,8 +3855,10 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
         }
         int ag = 0;
         i32* st = rec + c.off_agents;
+#pragma unroll UNR
         for (int t = 0; t < c.n_types; ++t) {
             const hftlob_agent_type_cfg& tc = c.types[t];
+#pragma unroll UNR
             for (int i = 0; i < tc.n_agents; ++i, ++ag) {
                 const i32 tid = wsub(tc.trader_id0, i);
                 const int nw = agent_words(tc);
@@ -3956,8 +3992,8 @@ DEV bool env_step_dev(const hftlob_env_cfg& c, int key_n, int ek, int e, const u
     }
 #endif
     if (all) {  // auto-reset: MARLEnv.step selects reset(key_reset) for state and obs
-        env_reset_dev<S>(c, key_reset, init_states, rec, emit ? obs_out + (size_t)e * c.n_agents * c.obs_stride : nullptr,
-                         B.vs, B.vt, ftime);
+        env_reset_dev<S, BAKED>(c_rt, key_reset, init_states, rec,
+                                emit ? obs_out + (size_t)e * c.n_agents * c.obs_stride : nullptr, B.vs, B.vt, ftime);
         return true;
     }
     if (l == 0) {
@@ -4056,8 +4092,11 @@ DEV void balance_prio(unsigned long long* row, u32 slot, unsigned long long r0, 
 // KB: 1 = the config derives its step keys in batches (kb_ok, checked by the launch code), 0 = it
 // does not, -1 = decided at run time (the general-size and rows-alias instantiations).  The metric
 // kernel is KB = 1: its loop holds no per-step key derivation.
-template <int S, int NFIX, bool RC, bool RA = false, int KB = -1>
-__global__ __launch_bounds__(64, 4) void k_env_rollout(hftlob_env_cfg c, int n_env, int key_e0, int key_n, int n_steps,
+// BAKED >= 0: the config is the baked one of that id (baked_cfg; env_variant launches it only for a
+// caller's config that equals it in every baked word): the step reads only the run-time words
+// from the kernel argument.
+template <int S, int NFIX, bool RC, bool RA = false, int KB = -1, int BAKED = -1>
+__global__ __launch_bounds__(64, 4) void k_env_rollout(hftlob_env_cfg c_arg, int n_env, int key_e0, int key_n, int n_steps,
                                                     int per_step, const u32* __restrict__ master,
                                                     u32* __restrict__ master_out, i32* __restrict__ actions_io,
                                                     const i32* __restrict__ msg_data,
@@ -4088,6 +4127,7 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout(hftlob_env_cfg c, int n_e
     const unsigned long long wt_start = __builtin_amdgcn_s_memtime(), wt_rstart = __builtin_amdgcn_s_memrealtime();
     const u32 wt_hwid = __builtin_amdgcn_s_getreg(0xF804), wt_xcc = __builtin_amdgcn_s_getreg(0x7814);
 #endif
+    const hftlob_env_cfg& c = baked_cfg<BAKED>(c_arg);
     // the key batches (step_keys_batch) live after the book in LDS
     const bool kbat = KB < 0 ? kb_ok(c) : KB == 1;
     const int kbw = kb_words(c);
@@ -4106,7 +4146,8 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout(hftlob_env_cfg c, int n_e
         const i32* md = msg_data;
         const i32* is = init_states;
         asm volatile("" : "+s"(cp), "+s"(st), "+s"(md), "+s"(is));
-        const hftlob_env_cfg& cc = *(const hftlob_env_cfg*)cp;
+        const hftlob_env_cfg& cr = *(const hftlob_env_cfg*)cp;  // (the run-time words when baked)
+        const hftlob_env_cfg& cc = baked_cfg<BAKED>(cr);
         STAMP(kb0);
         if (kbat && tb == 0) step_keys_batch<NFIX == 0>(cc, key_n, key_e0 + e, mk, imin_(KB_STEPS, n_steps - t), kbuf);
         STAMP(kb1);
@@ -4117,8 +4158,8 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout(hftlob_env_cfg c, int n_e
 #else
         const bool ox_info = ox;
 #endif
-        const bool reset = env_step_dev<S, NFIX, RC, RA, QT, KB>(
-            cc, key_n, key_e0 + e, e, nullptr, true, mk, actions_io ? actions_io + o * cc.action_words : nullptr, md,
+        const bool reset = env_step_dev<S, NFIX, RC, RA, QT, KB, false, BAKED>(
+            cr, key_n, key_e0 + e, e, nullptr, true, mk, actions_io ? actions_io + o * cc.action_words : nullptr, md,
             is, st, out.obs + o * cc.n_agents * cc.obs_stride, out.rewards + o * cc.n_agents, out.done_all + o,
             out.dones + o * cc.n_agents, ox_info && out.info ? out.info + o * cc.info_words : nullptr,
             ox && out.obs_raw ? out.obs_raw + o * cc.n_agents * cc.obs_stride : nullptr,
@@ -4377,6 +4418,14 @@ constexpr bool is_variant(int S, int NFIX, bool RC, bool RA) {
     HFTLOB_LISTED(SS, NF, RC, RA) P template __global__ void k_env_rollout<SS, NF, RC, RA, -1>(HFTLOB_ROLL_ARGS);
 #define HFTLOB_ROLL_KB(P, KB) \
     HFTLOB_LISTED(2, 100, false, false) P template __global__ void k_env_rollout<2, 100, false, false, KB>(HFTLOB_ROLL_ARGS);
+// the sampled rollout at (2, 100, false, false) with a baked config: one instantiation per entry
+// (id, KB) of HFTLOB_BAKED_KERNELS: the ids of baked_cfgs.inc the rollout has a kernel for, each with
+// its config's key-batch mode (kb_ok: 2_player_fq_fqc derives its keys in batches, the metric kernel;
+// 3_player_fq_fqc_dir has too many action rows for them).  The launch code takes an entry only for a
+// config whose variant and key-batch mode are these (env_rollout_launch).
+#define HFTLOB_BAKED_KERNELS(X) X(0, 1) X(1, 0)
+#define HFTLOB_ROLL_BAKED(P, B, KB) \
+    HFTLOB_LISTED(2, 100, false, false) P template __global__ void k_env_rollout<2, 100, false, false, KB, B>(HFTLOB_ROLL_ARGS);
 #define HFTLOB_RACT(P, SS, NF, RC, RA) \
     HFTLOB_LISTED(SS, NF, RC, RA) P template __global__ void k_env_rollout_actions<SS, NF, RC, RA>(HFTLOB_RACT_ARGS);
 #define HFTLOB_REVAL(P, SS, NF, RC, RA) \
@@ -4386,7 +4435,9 @@ constexpr bool is_variant(int S, int NFIX, bool RC, bool RA) {
 // variant's kernels extern and holds the small kernels and the C ABI.  Which part a kernel builds
 // in only balances the parallel build (part 1 stays the metric kernel alone: `make asm`); a listed
 // kernel that no part instantiates fails the link (-z defs).
-#define HFTLOB_NPARTS 17
+#define HFTLOB_NPARTS 19
+#define HFTLOB_PART18(P) HFTLOB_ROLL_BAKED(P, 0, 1)
+#define HFTLOB_PART19(P) HFTLOB_ROLL_BAKED(P, 1, 0)
 #define HFTLOB_PART1(P) HFTLOB_ROLL_KB(P, 1)
 #define HFTLOB_PART2(P) HFTLOB_STEP(P, 2, 100, false, false)
 #define HFTLOB_PART3(P) HFTLOB_ROLL(P, 1, 0, false, false) HFTLOB_STEP(P, 1, 0, false, false)
@@ -4419,6 +4470,9 @@ HFTLOB_CAT(HFTLOB_PART, HFTLOB_INST)()
 HFTLOB_VARIANTS(HFTLOB_X)
 #undef HFTLOB_X
 HFTLOB_ROLL_KB(extern, 1) HFTLOB_ROLL_KB(extern, 0)
+#define HFTLOB_X(B, KB) HFTLOB_ROLL_BAKED(extern, B, KB)
+HFTLOB_BAKED_KERNELS(HFTLOB_X)
+#undef HFTLOB_X
 #endif
 
 // ================================================================ C ABI
@@ -4649,12 +4703,32 @@ static bool reg_rows_ok(const hftlob_env_cfg* cfg) { return cfg->n_cancel_msgs +
 // 64 agent rows (reg_rows_ok); the others the general-size kernel of their slot sets.
 // kb: the config derives its rollout step keys in batches (the sampled
 // rollout's KB instantiations at (2, 100, false, false); decided in the kernel elsewhere).
+// baked: the id of the baked config (baked_cfgs.inc) the caller's config equals in every baked
+// word, or -1 (no such config, or the process-wide switch is off: hftlob_set_baked).  The sampled
+// rollout's persistent launch takes the baked instantiation of its metric kernel for it
+// (env_rollout_launch, HFTLOB_BAKED_KERNELS); every other launch ignores it.
 struct Variant {
     int S, nfix;
     bool rc, ra, kb;
+    int baked;
 };
+static int g_baked_on = 1;  // (read and written with __atomic builtins)
+// A masked compare: every word of the config but the run-time ones (n_windows, n_data_rows: zero in
+// the table) and tick_magic, which is the library's own (kernel_cfg sets it from tick_size, as the
+// generator does).  The struct is 32-bit words throughout, so it has no padding to compare.
+static_assert(alignof(hftlob_env_cfg) == 4 && sizeof(hftlob_env_cfg) % 4 == 0, "hftlob_env_cfg: 32-bit words only");
+static int baked_match(const hftlob_env_cfg* cfg) {
+    static const hftlob_env_cfg* const table[HFTLOB_N_BAKED] = HFTLOB_BAKED_TABLE;
+    hftlob_env_cfg k = kernel_cfg(cfg);
+    k.n_windows = 0;
+    k.n_data_rows = 0;
+    for (int i = 0; i < HFTLOB_N_BAKED; ++i)
+        if (memcmp(&k, table[i], sizeof k) == 0) return i;
+    return -1;
+}
 static Variant env_variant(const hftlob_env_cfg* cfg) {
     Variant v;
+    v.baked = __atomic_load_n(&g_baked_on, __ATOMIC_RELAXED) ? baked_match(cfg) : -1;
     v.rc = cfg->lob.cancel_mode >= 2;
     v.ra = use_rows_alias(cfg);
     v.nfix = nfix_kernel(cfg) && (v.ra || reg_rows_ok(cfg)) ? 100 : 0;
@@ -4712,6 +4786,12 @@ static int env_rollout_launch(const hftlob_env_cfg* cfg, int n_env, int key_e0, 
         [](auto V, const Variant& v) {
             using T = decltype(V);
             // (the exception to the list: the 100/100 kernel without alias comes per key-batch mode)
+            if constexpr (T::S == 2 && T::NFIX == 100 && !T::RC && !T::RA) {  // (the baked kernels' variant)
+#define HFTLOB_X(B, KB) \
+                if (v.baked == B && v.kb == (KB == 1)) return k_env_rollout<2, 100, false, false, KB, B>;
+                HFTLOB_BAKED_KERNELS(HFTLOB_X)
+#undef HFTLOB_X
+            }
             if constexpr (T::NFIX > 0 && !T::RA)
                 return v.kb ? k_env_rollout<T::S, T::NFIX, T::RC, T::RA, 1> : k_env_rollout<T::S, T::NFIX, T::RC, T::RA, 0>;
             else
@@ -4823,6 +4903,15 @@ int hftlob_env_launch_info(const hftlob_env_cfg* cfg, hftlob_launch_info* out) {
     out->tick_magic = kernel_cfg(cfg).tick_magic;
     out->key_batch = v.kb ? 1 : 0;
     return HFTLOB_OK;
+}
+
+int hftlob_env_baked_id(const hftlob_env_cfg* cfg) {
+    if (!cfg || check_env(cfg)) return -1;
+    return env_variant(cfg).baked;
+}
+
+int hftlob_set_baked(int on) {
+    return __atomic_exchange_n(&g_baked_on, on ? 1 : 0, __ATOMIC_RELAXED);
 }
 
 int hftlob_rollout_prepare(int n_slices, void* stream) {

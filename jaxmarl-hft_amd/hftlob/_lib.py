@@ -31,7 +31,7 @@ EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob
            "hftlob_book_process_depth", "hftlob_env_reset",
            "hftlob_env_step", "hftlob_env_step_sampled", "hftlob_env_rollout_sampled", "hftlob_rollout_prepare",
            "hftlob_env_rollout_actions", "hftlob_env_rollout_eval",
-           "hftlob_env_lds_bytes", "hftlob_env_launch_info",
+           "hftlob_env_lds_bytes", "hftlob_env_launch_info", "hftlob_env_baked_id", "hftlob_set_baked",
            "hftlob_sample_actions", "hftlob_split_keys", "hftlob_gru_scan_fwd", "hftlob_gru_scan_bwd",
            "hftlob_policy_step")
 
@@ -79,7 +79,11 @@ def lib() -> C.CDLL:
     L.hftlob_env_lds_bytes.restype = i32
     L.hftlob_env_launch_info.argtypes = [C.POINTER(EnvCfg), C.POINTER(LaunchInfo)]
     L.hftlob_env_launch_info.restype = i32
-    L.hftlob_sample_actions.argtypes = [C.POINTER(EnvCfg), i32, vp, vp, vp]
+    L.hftlob_env_baked_id.argtypes = [C.POINTER(EnvCfg)]
+    L.hftlob_env_baked_id.restype = i32
+    L.hftlob_set_baked.argtypes = [i32]
+    L.hftlob_set_baked.restype = i32
+    L.hftlob_sample_actions.argtypes =[C.POINTER(EnvCfg), i32, vp, vp, vp]
     L.hftlob_sample_actions.restype = i32
     L.hftlob_split_keys.argtypes = [i32, i32, i32, vp, vp, vp]
     L.hftlob_split_keys.restype = i32
@@ -94,6 +98,12 @@ def lib() -> C.CDLL:
         raise RuntimeError(f"libhftlob ABI {L.hftlob_version()} != {ABI_VERSION}")
     _lib = L
     return L
+
+
+def set_baked(on: bool) -> bool:
+    """hftlob_set_baked: the process-wide switch of the baked-config kernels (default on; off = every
+    launch takes the general kernels, for A/B runs and tests).  Returns the previous setting."""
+    return bool(lib().hftlob_set_baked(int(bool(on))))
 
 
 def check(rc: int) -> None:

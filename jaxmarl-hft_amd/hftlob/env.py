@@ -473,6 +473,14 @@ class MARLEnv:
         _lib.check(_lib.lib().hftlob_env_launch_info(C.byref(self.cfg_c), C.byref(info)))
         return {k: int(getattr(info, k)) for k, _ in info._fields_}
 
+    def baked_id(self) -> int:
+        """The id of the baked config (the library's compile-time copy of a builtin config) this
+        env's config equals in every word but the day's, or -1 (hftlob_env_baked_id): no such
+        config, or the switch ``_lib.set_baked`` is off.  rollout_sampled's persistent launch
+        (n_slices = 0) then runs a kernel specialised for the config where the library has one
+        (ids 0 and 1: 2_player_fq_fqc, 3_player_fq_fqc_dir); the results do not depend on it."""
+        return int(_lib.lib().hftlob_env_baked_id(C.byref(self.cfg_c)))
+
     def _tuned_device(self) -> bool:
         if not torch.cuda.is_available():
             return True

@@ -18,7 +18,7 @@ def main(path, kname):
     for ln in body:
         m = re.search(r"v_writelane_b32 (v\d+), s\d+, \d+$", ln.strip())
         if m:
-            if int(m.group(1)[1:]) >= 120 and ln.strip().endswith(tuple(str(k) for k in range(64))):
+            if int(m.group(1)[1:]) >= 110 and ln.strip().endswith(tuple(str(k) for k in range(64))):
                 spill_v.add(m.group(1))
     # loop membership: block -> innermost header; header -> parent
     parent, cur, counts = {}, None, defaultdict(lambda: defaultdict(int))
