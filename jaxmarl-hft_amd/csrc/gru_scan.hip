@@ -23,25 +23,11 @@
 // k, and a sum does not depend on the permutation beyond its rounding order.
 // What bounds the forward is that load path, not the MFMAs: a lane's B
 // operand is a row of W_hh, so every quarter-wave of a load touches 16 rows.
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/hftlob.h"
-#include "hftlob_internal.h"
+#include "hftlob_tile.h"  // f32x4, ld4 / st4 / splat, TILE and the MFMA operand maps
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int TILE = 16;  // batch rows per workgroup: the M of mfma_f32_16x16x4f32
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ f32x4 splat(float x) { return f32x4{x, x, x, x}; }
-
-// MFMA operand maps (16x16x4 f32): lane l gives A[row l & 15][k l >> 4] and B[k l >> 4][col l & 15];
-// accumulator register i of lane l is D[row 4 (l >> 4) + i][col l & 15].
 
 template <int H, int CB>
 __global__ __launch_bounds__(64 * (H / 16 / CB)) void k_gru_scan_fwd(
@@ -261,11 +247,6 @@ int check_shape(int T, int B, int H) {
     if (T < 1 || B < 1) return hftlob_fail(HFTLOB_ESHAPE, "gru_scan: T and B must be >= 1");
     if (H != 64 && H != 128 && H != 256) return hftlob_fail(HFTLOB_ESHAPE, "gru_scan: H must be 64, 128 or 256");
     return HFTLOB_OK;
-}
-
-int launch_status() {
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? HFTLOB_OK : hftlob_fail(HFTLOB_ELAUNCH, hipGetErrorString(err));
 }
 
 }  // namespace

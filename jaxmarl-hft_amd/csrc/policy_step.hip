@@ -3,8 +3,8 @@
 //
 // One ActorCriticRNN step (jaxrl/MARL/ippo_rnn_JAXMARL.py:53-78, 183-256) for a batch of actors as
 // one launch: embedding, GRU cell, critic and actor heads, softmax, the sample (or the argmax) and
-// its log-probability.  It is shaped like k_gru_scan_fwd (gru_scan.hip): a workgroup owns a tile of
-// 16 batch rows, the M side of the f32-input 16x16x4 MFMA, and waits on no other workgroup.  Every
+// its log-probability.  A workgroup owns a tile of 16 batch rows, the M side of the f32-input
+// 16x16x4 MFMA (hftlob_tile.h, shared with gru_scan.hip), and waits on no other workgroup.  Every
 // product is that MFMA, so every dot product is a k-ordered fmaf chain in float32.
 //
 // The layers chain through LDS, three padded [16][W + 4] buffers:
@@ -19,36 +19,30 @@
 //              columns of those j, so the gate math runs in registers on the accumulators
 //   heads      critic1 (FC columns) and actor1 (H columns) read the same h: their (FC + H) / 16
 //              column blocks are dealt over the waves, a wave's blocks run together on one A operand
-//   outputs    wave 0: logits = relu(actor1) . w_a2^T as one MFMA column block (A <= 16), then the
-//              softmax, the Gumbel noise and the argmax over 16-lane rows; wave 1: value, a 16-row
-//              dot product over FC reduced across the lane quarters.  The multi-head operator's K <= 4
-//              heads (:80-100, 259-281) are four such column blocks on the one A operand in wave 0, each
-//              with its own row offset, width, key and counters; the log-probs add up in head order
+//   outputs    wave 0: a head's logits = relu(actor1) . w_a2[its rows]^T are one MFMA column block (<= 16
+//              logits), then its softmax, Gumbel noise and first argmax over 16-lane rows.  The heads
+//              (:80-100, 259-281; one for hftlob_policy_step, K <= 4 for the multi-head operator) are
+//              NHD such blocks on the one A operand, each with its own row offset, width, key and
+//              counters; the log-probs add up in head order.  wave 1: value, a 16-row dot product
+//              over FC reduced across the lane quarters
 //
 // The weights (about 2.1 MB at 256 / 256) stream from L2 as float4 per lane into register buffers
-// two chunks of 32 k ahead of the MFMAs that use them, with the forward scan's operand maps (lane
-// quarter q of chunk c has k = 32 c + 8 q + 0..7 for both operands).  The three lessons of the scan
-// hold here too: loads are unconditional at clamped indices, no branch sits between a prefetch and
+// two chunks of 32 k ahead of the MFMAs that use them; the k order inside a chunk is permuted so that
+// both operands are 16-byte reads (lane quarter q of chunk c has k = 32 c + 8 q + 0..7, as in
+// k_gru_scan_fwd).  Loads are unconditional at clamped indices, no branch sits between a prefetch and
 // its wait, and a sched_barrier keeps the loads where they are issued.  A stage's first chunks are
 // requested before the previous stage's epilogue and barrier.
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/hftlob.h"
-#include "hftlob_internal.h"
+#include "hftlob_tile.h"  // f32x4, ld4 / splat, sigmoidf_, TILE and the MFMA operand maps
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32;
 
-constexpr int TILE = 16;  // batch rows per workgroup: the M of mfma_f32_16x16x4f32
 constexpr int PF = 2;     // weight chunks in flight per stream
 constexpr int DMAX = 64;  // obs columns in LDS (D <= 64, zero-padded)
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ f32x4 splat(float x) { return f32x4{x, x, x, x}; }
 __device__ __forceinline__ u32 rotl32(u32 x, int r) { return (x << r) | (x >> (32 - r)); }
 
 // threefry2x32 with 20 rounds (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3"), as JAX
@@ -78,9 +72,6 @@ __device__ __forceinline__ float gumbel_from_bits(u32 bits) {
     const float u = fmaxf(tiny, f * (1.0f - tiny) + tiny);
     return -logf(-logf(u));
 }
-
-// MFMA operand maps (16x16x4 f32): lane l gives A[row l & 15][k l >> 4] and B[k l >> 4][col l & 15];
-// accumulator register i of lane l is D[row 4 (l >> 4) + i][col l & 15].
 
 // the first PF chunks of N weight rows (wp[n] is the lane's row, already at its quarter's 8 q)
 template <int N>
@@ -140,7 +131,7 @@ struct Shape {
 
 constexpr int MAXK = 4;  // action heads of the multi-head operator: the logits stage's column blocks
 
-// the heads of hftlob_policy_step_multi, by value: head k has nv[k] logits from row off[k] of w_a2; the
+// the action heads, by value: head k has nv[k] logits from row off[k] of w_a2, S logits in all; the
 // entries past K repeat head K - 1 (their loads stay in bounds, their results are dropped)
 struct Heads {
     int K, S;
@@ -170,21 +161,12 @@ __device__ __forceinline__ void head_pick(float x, float sc, bool live_a, int l,
     lp = xa - mx - logf(sum);
 }
 
-// The step of a tile.  NHD == 1 is hftlob_policy_step (the head argument is A: one head of A logits,
-// key [2]); NHD == MAXK is hftlob_policy_step_multi (the head argument is a Heads: K heads, key [K][2],
-// action [B][K], logits [B][S]), whose logits stage runs MAXK column blocks on the one A operand in wave 0
-template <int NHD>
-struct HeadArg {
-    typedef Heads type;
-};
-template <>
-struct HeadArg<1> {
-    typedef int type;
-};
-
+// The step of a tile: hd.K <= NHD heads, key [K][2], action [B][K], logits [B][S].  NHD is the number of
+// column blocks the logits stage runs on the one A operand in wave 0: 1 for hftlob_policy_step (one
+// head of A logits, so action [B] and logits [B][A]), MAXK for hftlob_policy_step_multi
 template <int H, int FC, int NHD>
 __global__ __launch_bounds__((Shape<H, FC>::NT)) void k_policy_step(
-    int B, int D, typename HeadArg<NHD>::type hd, hftlob_policy_weights W, const float* __restrict__ obs,
+    int B, int D, Heads hd, hftlob_policy_weights W, const float* __restrict__ obs,
     const uint8_t* __restrict__ done, const float* h_in, float* h_out, int mode, const u32* __restrict__ key,
     int32_t* __restrict__ action, float* __restrict__ log_prob, float* __restrict__ value,
     float* __restrict__ logits) {
@@ -305,13 +287,12 @@ __global__ __launch_bounds__((Shape<H, FC>::NT)) void k_policy_step(
     stream<NBH, H>(ha, wh, wpc, wpc, bh + li * SH + 8 * q);
 
     // the logits' first chunks (wave 0 uses them), in flight under the stores and the barrier; rows
-    // of w_a2 past A repeat row A - 1 and their columns are masked below
+    // of w_a2 past a head's last repeat that row and their columns are masked below
     int arow[NHD];
     const float* wpa[NHD];
 #pragma unroll
     for (int n = 0; n < NHD; ++n) {
-        if constexpr (NHD == 1) arow[n] = min(li, hd - 1);
-        else arow[n] = hd.off[n] + min(li, hd.nv[n] - 1);
+        arow[n] = hd.off[n] + min(li, hd.nv[n] - 1);
         wpa[n] = W.w_a2 + (size_t)arow[n] * H + 8 * q;
     }
     f32x4 wa[PF][NHD][2];
@@ -345,102 +326,68 @@ __global__ __launch_bounds__((Shape<H, FC>::NT)) void k_policy_step(
 #pragma unroll
     for (int n = 0; n < NHD; ++n) lg[n] = splat(W.b_a2[arow[n]]);
     stream<NHD, H>(lg, wa, wpa, wpa, bp + li * SH + 8 * q);
-    if constexpr (NHD == 1) {
-        const int A = hd;
-        const bool live_a = li < A;
+    // head n's noise is drawn from key[n] at counter (0, b nv[n] + a); log_prob adds the heads in order
+    float lps[4];
+#pragma unroll
+    for (int n = 0; n < NHD; ++n) {
+        if (n >= hd.K) break;  // wave-uniform, and no load is in flight any more
+        const int An = hd.nv[n];
+        const bool live_a = li < An;
         u32 k0 = 0, k1 = 0;
         if (mode == 0) {
-            k0 = key[0];
-            k1 = key[1];
+            k0 = key[2 * n];
+            k1 = key[2 * n + 1];
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int b = b0 + 4 * q + i;
             const bool live = b < B;
-            const float x = lg[0][i];
-            if (logits && live && live_a) logits[(size_t)b * A + li] = x;
-            float sc = x;  // the score whose first argmax is the action
-            if (mode == 0) sc = x + gumbel_from_bits(threefry_bits(k0, k1, 0u, (u32)min(b, B - 1) * (u32)A + (u32)li));
-            sc = live_a ? sc : -INFINITY;
-            int idx = li;
-            float mx = live_a ? x : -INFINITY;
-#pragma unroll
-            for (int m = 1; m < 16; m <<= 1) {
-                const float os = __shfl_xor(sc, m);
-                const int oi = __shfl_xor(idx, m);
-                if (os > sc || (os == sc && oi < idx)) {
-                    sc = os;
-                    idx = oi;
-                }
-                mx = fmaxf(mx, __shfl_xor(mx, m));
-            }
-            float sum = live_a ? expf(x - mx) : 0.0f;
-#pragma unroll
-            for (int m = 1; m < 16; m <<= 1) sum += __shfl_xor(sum, m);
-            const float xa = __shfl(x, (l & 48) | idx);
-            if (live && li == 0) {
-                action[b] = idx;
-                log_prob[b] = xa - mx - logf(sum);
-            }
-        }
-    } else {
-        // head n's noise is drawn from key[n] at counter (0, b nv[n] + a); log_prob adds the heads in order
-        float lps[4];
-#pragma unroll
-        for (int n = 0; n < NHD; ++n) {
-            if (n >= hd.K) break;  // wave-uniform, and no load is in flight any more
-            const int An = hd.nv[n];
-            const bool live_a = li < An;
-            u32 k0 = 0, k1 = 0;
-            if (mode == 0) {
-                k0 = key[2 * n];
-                k1 = key[2 * n + 1];
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int b = b0 + 4 * q + i;
-                const bool live = b < B;
-                const float x = lg[n][i];
-                if (logits && live && live_a) logits[(size_t)b * hd.S + hd.off[n] + li] = x;
-                float sc = x;
-                if (mode == 0)
-                    sc = x + gumbel_from_bits(threefry_bits(k0, k1, 0u, (u32)min(b, B - 1) * (u32)An + (u32)li));
-                int idx;
-                float lp;
-                head_pick(x, sc, live_a, l, li, idx, lp);
-                lps[i] = n == 0 ? lp : lps[i] + lp;
-                if (live && li == 0) action[(size_t)b * hd.K + n] = idx;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int b = b0 + 4 * q + i;
-            if (b < B && li == 0) log_prob[b] = lps[i];
+            const float x = lg[n][i];
+            if (logits && live && live_a) logits[(size_t)b * hd.S + hd.off[n] + li] = x;
+            float sc = x;
+            if (mode == 0)
+                sc = x + gumbel_from_bits(threefry_bits(k0, k1, 0u, (u32)min(b, B - 1) * (u32)An + (u32)li));
+            int idx;
+            float lp;
+            head_pick(x, sc, live_a, l, li, idx, lp);
+            lps[i] = n == 0 ? lp : lps[i] + lp;
+            if (live && li == 0) action[(size_t)b * hd.K + n] = idx;
         }
     }
-}
-
-int launch_status() {
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? HFTLOB_OK : hftlob_fail(HFTLOB_ELAUNCH, hipGetErrorString(err));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int b = b0 + 4 * q + i;
+        if (b < B && li == 0) log_prob[b] = lps[i];
+    }
 }
 
 bool size_ok(int n) { return n == 64 || n == 128 || n == 256; }
 bool misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
 
-// the checks the two operators share, in the order hftlob_policy_step has always made them: the sizes
-// before the head's, the rest after
-int check_sizes(int B, int D, int FC, int H) {
+#define HFTLOB_POLICY_CASES   \
+    HFTLOB_POLICY_CASE(64, 64)    \
+    HFTLOB_POLICY_CASE(64, 128)   \
+    HFTLOB_POLICY_CASE(64, 256)   \
+    HFTLOB_POLICY_CASE(128, 64)   \
+    HFTLOB_POLICY_CASE(128, 128)  \
+    HFTLOB_POLICY_CASE(128, 256)  \
+    HFTLOB_POLICY_CASE(256, 64)   \
+    HFTLOB_POLICY_CASE(256, 128)  \
+    HFTLOB_POLICY_CASE(256, 256)
+
+// Both operators' checks and launch, with NHD logits blocks.  The checks run in the order they always
+// have: the sizes, then head_check (the operator's own check of K and nv, which are read only after
+// it passes), then the mode, the pointers and the alignment
+template <int NHD, class HeadCheck>
+int policy_launch(int B, int D, int FC, int H, int K, const int* nv, HeadCheck head_check,
+                  const hftlob_policy_weights* w, const float* obs, const uint8_t* done, const float* h_in, float* h_out,
+                  int mode, const uint32_t* key, int32_t* action, float* log_prob, float* value, float* logits,
+                  void* stream) {
     if (B < 1) return hftlob_fail(HFTLOB_ESHAPE, "policy_step: B must be >= 1");
     if (!size_ok(H)) return hftlob_fail(HFTLOB_ESHAPE, "policy_step: H must be 64, 128 or 256");
     if (!size_ok(FC)) return hftlob_fail(HFTLOB_ESHAPE, "policy_step: FC must be 64, 128 or 256");
     if (D < 1 || D > DMAX) return hftlob_fail(HFTLOB_ESHAPE, "policy_step: D must be in 1..64");
-    return HFTLOB_OK;
-}
-
-int check_rest(int mode, const hftlob_policy_weights* w, const float* obs, const uint8_t* done, const float* h_in,
-               const float* h_out, const uint32_t* key, const int32_t* action, const float* log_prob,
-               const float* value) {
+    if (int rc = head_check()) return rc;
     if (mode != 0 && mode != 1) return hftlob_fail(HFTLOB_EINVAL, "policy_step: mode must be 0 (sample) or 1 (argmax)");
     if (!w) return hftlob_fail(HFTLOB_ENULL, "policy_step: w (the weight struct) is NULL");
     if (!w->w_embed || !w->b_embed || !w->w_ih || !w->b_ih || !w->w_hh || !w->b_hh || !w->w_c1 || !w->b_c1 ||
@@ -456,68 +403,54 @@ int check_rest(int mode, const hftlob_policy_weights* w, const float* obs, const
     if (!value) return hftlob_fail(HFTLOB_ENULL, "policy_step: value is NULL");
     if (misaligned(w->w_ih) || misaligned(w->w_hh) || misaligned(w->w_c1) || misaligned(w->w_a1) || misaligned(w->w_a2))
         return hftlob_fail(HFTLOB_EINVAL, "policy_step: w_ih, w_hh, w_c1, w_a1 and w_a2 must be 16-byte aligned");
-    return HFTLOB_OK;
-}
-
-}  // namespace
-
-#define HFTLOB_POLICY_CASES   \
-    HFTLOB_POLICY_CASE(64, 64)    \
-    HFTLOB_POLICY_CASE(64, 128)   \
-    HFTLOB_POLICY_CASE(64, 256)   \
-    HFTLOB_POLICY_CASE(128, 64)   \
-    HFTLOB_POLICY_CASE(128, 128)  \
-    HFTLOB_POLICY_CASE(128, 256)  \
-    HFTLOB_POLICY_CASE(256, 64)   \
-    HFTLOB_POLICY_CASE(256, 128)  \
-    HFTLOB_POLICY_CASE(256, 256)
-
-extern "C" int hftlob_policy_step(int B, int D, int FC, int H, int A, const hftlob_policy_weights* w, const float* obs,
-                                  const uint8_t* done, const float* h_in, float* h_out, int mode, const uint32_t* key,
-                                  int32_t* action, float* log_prob, float* value, float* logits, void* stream) {
-    if (int rc = check_sizes(B, D, FC, H)) return rc;
-    if (A < 1 || A > 16) return hftlob_fail(HFTLOB_ESHAPE, "policy_step: A must be in 1..16");
-    if (int rc = check_rest(mode, w, obs, done, h_in, h_out, key, action, log_prob, value)) return rc;
+    static_assert(NHD <= MAXK, "Heads holds MAXK entries");
+    Heads hd;
+    hd.K = K;
+    hd.S = 0;
+    for (int k = 0; k < K; ++k) {
+        hd.nv[k] = nv[k];
+        hd.off[k] = hd.S;
+        hd.S += nv[k];
+    }
+    for (int k = K; k < MAXK; ++k) {  // the entries past K repeat head K - 1
+        hd.nv[k] = hd.nv[K - 1];
+        hd.off[k] = hd.off[K - 1];
+    }
     const dim3 grid((unsigned)((B + TILE - 1) / TILE));
     hipStream_t s = (hipStream_t)stream;
 #define HFTLOB_POLICY_CASE(h, fc)                                                                                     \
     if (H == h && FC == fc)                                                                                           \
-        k_policy_step<h, fc, 1><<<grid, Shape<h, fc>::NT, 0, s>>>(B, D, A, *w, obs, done, h_in, h_out, mode, key, action, \
-                                                                  log_prob, value, logits);
+        k_policy_step<h, fc, NHD><<<grid, Shape<h, fc>::NT, 0, s>>>(B, D, hd, *w, obs, done, h_in, h_out, mode, key,  \
+                                                                    action, log_prob, value, logits);
     HFTLOB_POLICY_CASES
 #undef HFTLOB_POLICY_CASE
     return launch_status();
+}
+
+}  // namespace
+
+extern "C" int hftlob_policy_step(int B, int D, int FC, int H, int A, const hftlob_policy_weights* w, const float* obs,
+                                  const uint8_t* done, const float* h_in, float* h_out, int mode, const uint32_t* key,
+                                  int32_t* action, float* log_prob, float* value, float* logits, void* stream) {
+    const auto head_check = [&] {
+        return A < 1 || A > 16 ? hftlob_fail(HFTLOB_ESHAPE, "policy_step: A must be in 1..16") : HFTLOB_OK;
+    };
+    return policy_launch<1>(B, D, FC, H, 1, &A, head_check, w, obs, done, h_in, h_out, mode, key, action, log_prob, value,
+                            logits, stream);
 }
 
 extern "C" int hftlob_policy_step_multi(int B, int D, int FC, int H, int K, const int* nvec,
                                         const hftlob_policy_weights* w, const float* obs, const uint8_t* done,
                                         const float* h_in, float* h_out, int mode, const uint32_t* keys, int32_t* action,
                                         float* log_prob, float* value, float* logits, void* stream) {
-    if (int rc = check_sizes(B, D, FC, H)) return rc;
-    if (K < 1 || K > MAXK) return hftlob_fail(HFTLOB_ESHAPE, "policy_step_multi: K must be in 1..4");
-    if (!nvec) return hftlob_fail(HFTLOB_ENULL, "policy_step_multi: nvec is NULL");
-    Heads hd;
-    hd.K = K;
-    hd.S = 0;
-    for (int k = 0; k < K; ++k) {
-        if (nvec[k] < 1 || nvec[k] > 16)
-            return hftlob_fail(HFTLOB_ESHAPE, "policy_step_multi: every nvec entry must be in 1..16");
-        hd.nv[k] = nvec[k];
-        hd.off[k] = hd.S;
-        hd.S += nvec[k];
-    }
-    for (int k = K; k < MAXK; ++k) {  // the blocks past K repeat head K - 1
-        hd.nv[k] = hd.nv[K - 1];
-        hd.off[k] = hd.off[K - 1];
-    }
-    if (int rc = check_rest(mode, w, obs, done, h_in, h_out, keys, action, log_prob, value)) return rc;
-    const dim3 grid((unsigned)((B + TILE - 1) / TILE));
-    hipStream_t s = (hipStream_t)stream;
-#define HFTLOB_POLICY_CASE(h, fc)                                                                                  \
-    if (H == h && FC == fc)                                                                                        \
-        k_policy_step<h, fc, MAXK><<<grid, Shape<h, fc>::NT, 0, s>>>(B, D, hd, *w, obs, done, h_in, h_out, mode, keys, \
-                                                                     action, log_prob, value, logits);
-    HFTLOB_POLICY_CASES
-#undef HFTLOB_POLICY_CASE
-    return launch_status();
+    const auto head_check = [&] {
+        if (K < 1 || K > MAXK) return hftlob_fail(HFTLOB_ESHAPE, "policy_step_multi: K must be in 1..4");
+        if (!nvec) return hftlob_fail(HFTLOB_ENULL, "policy_step_multi: nvec is NULL");
+        for (int k = 0; k < K; ++k)
+            if (nvec[k] < 1 || nvec[k] > 16)
+                return hftlob_fail(HFTLOB_ESHAPE, "policy_step_multi: every nvec entry must be in 1..16");
+        return (int)HFTLOB_OK;
+    };
+    return policy_launch<MAXK>(B, D, FC, H, K, nvec, head_check, w, obs, done, h_in, h_out, mode, keys, action, log_prob,
+                               value, logits, stream);
 }

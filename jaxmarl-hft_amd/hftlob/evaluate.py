@@ -249,14 +249,13 @@ def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: boo
     holds one ``ActorCriticRNN`` per agent type (``hftlob.train.ippo.load_policy``).  The reset and
     the env step keys are that function's chain unchanged; the key its chain leaves unused each step
     (:func:`eval_keys`' "unused action sample") is the step's policy key, split once more per agent
-    type.  Each step is one fused ``policy_step`` per type, ``policy_step_multi`` for the net of a
-    MultiDiscrete type (the argmax if ``greedy``, else a ``jax.random.categorical`` sample per head),
-    followed by ``env.step``; the carries start at zero and are reset by each actor's done.  The
-    rewards, raw info words and global dones of ``chunk`` steps are kept and reduced with
-    :func:`reduce_steps`, the stats carried from chunk to chunk.  The env must be built with
-    ``return_info=True``."""
+    type.  Each step is one fused policy step per type (``train.policy.policy_step_net``: the argmax
+    if ``greedy``, else a ``jax.random.categorical`` sample per head), followed by ``env.step``; the
+    carries start at zero and are reset by each actor's done.  The rewards, raw info words and global
+    dones of ``chunk`` steps are kept and reduced with :func:`reduce_steps`, the stats carried from
+    chunk to chunk.  The env must be built with ``return_info=True``."""
     from .env import split_keys
-    from .train.policy import GREEDY, SAMPLE, policy_step, policy_step_multi
+    from .train.policy import GREEDY, SAMPLE, policy_step_net
     if n_envs < 1 or n_steps < 1 or chunk < 1:
         raise ValueError("n_envs, n_steps and chunk must be >= 1")
     if not getattr(env, "return_info", False):
@@ -287,12 +286,8 @@ def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: boo
         for t in range(T):
             actions = []
             for i, net in enumerate(nets):
-                key = pol[t, i] if mode == SAMPLE else None
-                if net.nvec is None:
-                    a = policy_step(net, obs[i], done[i], h[i], mode, key=key)[1]
-                else:   # a MultiDiscrete type: one action word per head, [E, n_t, K]
-                    a = policy_step_multi(net, obs[i], done[i], h[i], mode, net.nvec, key=key)[1]
-                actions.append(a.view(E, counts[i], *a.shape[1:]))
+                a = policy_step_net(net, obs[i], done[i], h[i], mode, key=pol[t, i] if mode == SAMPLE else None)[1]
+                actions.append(a.view(E, counts[i], *a.shape[1:]))   # [E, n_t], or [E, n_t, K] of a MultiDiscrete type
             o, state, r, d, _ = env.step(keys[t], state, actions, params)
             info[t].copy_(env.last_info_words)
             done_all[t].copy_(d["__all__"])

@@ -48,8 +48,7 @@ import torch.nn.functional as F
 
 from ..env import MARLEnv, split_keys
 from .gru import SUPPORTED_HIDDEN, gru_scan, gru_scan_supported
-from .policy import (MAX_ACTIONS, MAX_HEADS, MAX_OBS_DIM, SAMPLE, policy_step, policy_step_multi,
-                     policy_step_multi_supported, policy_step_supported)
+from .policy import MAX_ACTIONS, MAX_HEADS, MAX_OBS_DIM, SAMPLE, policy_step_multi_supported, policy_step_net
 
 
 def _per_type(v, n: int) -> list:
@@ -86,8 +85,8 @@ class ActorCriticRNN(nn.Module):
         super().__init__()
         n_actions = head_sizes(n_actions)
         self.nvec = n_actions if isinstance(n_actions, list) else None
-        if self.nvec is not None:
-            n_actions = sum(self.nvec)
+        self.heads: List[int] = [n_actions] if self.nvec is None else self.nvec   # the heads' widths, one or more
+        n_actions = sum(self.heads)
         self.embed = nn.Linear(obs_dim, fc)
         self.gru = nn.GRUCell(fc, hidden)
         self.critic1, self.critic2 = nn.Linear(hidden, fc), nn.Linear(fc, 1)
@@ -96,12 +95,17 @@ class ActorCriticRNN(nn.Module):
                      (self.actor2, 0.01)):
             nn.init.orthogonal_(m.weight, g)
             nn.init.zeros_(m.bias)
-        if self.nvec is not None:
+        if len(self.heads) > 1:   # (one head is the layer just initialised: no further draw from the generator)
             with torch.no_grad():
-                for blk in self.actor2.weight.split(self.nvec, 0):
+                for blk in self.actor2.weight.split(self.heads, 0):
                     blk.copy_(nn.init.orthogonal_(torch.empty_like(blk), 0.01))
         self.hidden = hidden
         self.fused = False   # forward's scan as one HIP launch per direction (train.gru.gru_scan); the trainer sets it
+
+    def action_shape(self, *lead: int) -> tuple:
+        """The shape of the public action tensor of ``lead`` actors: one word each for a Discrete space,
+        K words for a MultiDiscrete one (the one place that tells the two apart)."""
+        return lead if self.nvec is None else lead + (len(self.heads),)
 
     def step(self, h: torch.Tensor, obs: torch.Tensor, done: torch.Tensor):
         """One time step for a batch of actors: (new carry, logits, value)."""
@@ -182,26 +186,26 @@ def _loss_tail(log_prob, entropy, values, rb_value, rb_log_prob, gae, targets, c
     return total, value_loss, actor_loss, entropy, approx_kl, clip_frac
 
 
-def ppo_loss(logits, values, rb_action, rb_value, rb_log_prob, gae, targets, clip_eps: float, vf_coef: float,
-             ent_coef: float):
-    """_loss_fn (:718-765) -> (total, value_loss, actor_loss, entropy, approx_kl, clip_frac)."""
-    logp_all = F.log_softmax(logits, -1)
-    log_prob = logp_all.gather(-1, rb_action.long().unsqueeze(-1)).squeeze(-1)
-    entropy = -(logp_all.exp() * logp_all).sum(-1)
-    return _loss_tail(log_prob, entropy, values, rb_value, rb_log_prob, gae, targets, clip_eps, vf_coef, ent_coef)
-
-
 def ppo_loss_multi(logits, values, rb_action, rb_value, rb_log_prob, gae, targets, clip_eps: float, vf_coef: float,
                    ent_coef: float, nvec: Sequence[int]):
-    """``ppo_loss`` under MultiCategorical (:259-281): logits [..., sum(nvec)] are the heads' logits side
-    by side, rb_action [..., K]; log_prob is the sum of the heads' log-probabilities at their actions,
-    entropy the sum of the heads' entropies.  The rest is ``ppo_loss``'s."""
-    log_prob, entropy = 0.0, 0.0
+    """_loss_fn (:718-765) under MultiCategorical (:259-281) -> (total, value_loss, actor_loss, entropy,
+    approx_kl, clip_frac): logits [..., sum(nvec)] are the heads' logits side by side, rb_action [..., K];
+    log_prob is the sum of the heads' log-probabilities at their actions, entropy the sum of the heads'
+    entropies, both starting from the first head's (one head adds nothing)."""
+    log_prob = entropy = None
     for k, lg in enumerate(logits.split(list(nvec), dim=-1)):
         logp_all = F.log_softmax(lg, -1)
-        log_prob = log_prob + logp_all.gather(-1, rb_action[..., k].long().unsqueeze(-1)).squeeze(-1)
-        entropy = entropy - (logp_all.exp() * logp_all).sum(-1)
+        lp = logp_all.gather(-1, rb_action[..., k].long().unsqueeze(-1)).squeeze(-1)
+        ent = -(logp_all.exp() * logp_all).sum(-1)
+        log_prob, entropy = (lp, ent) if k == 0 else (log_prob + lp, entropy + ent)
     return _loss_tail(log_prob, entropy, values, rb_value, rb_log_prob, gae, targets, clip_eps, vf_coef, ent_coef)
+
+
+def ppo_loss(logits, values, rb_action, rb_value, rb_log_prob, gae, targets, clip_eps: float, vf_coef: float,
+             ent_coef: float):
+    """``ppo_loss_multi`` for a Discrete space: one head of all the logits, rb_action [...]."""
+    return ppo_loss_multi(logits, values, rb_action[..., None], rb_value, rb_log_prob, gae, targets, clip_eps, vf_coef,
+                          ent_coef, [logits.shape[-1]])
 
 
 def linear_schedule(lr: float, count: int, n_minibatches: int, n_epochs: int, n_updates: int) -> float:
@@ -267,14 +271,12 @@ class IPPOTrainer:
             if self.device.type != "cuda":
                 raise ValueError(f"FUSED_POLICY needs a GPU device, got {self.device}")
             for i, n in enumerate(self.nets):
-                D, A = n.embed.in_features, n.actor2.out_features
-                ok = (policy_step_supported(D, c["FC_DIM_SIZE"], c["GRU_HIDDEN_DIM"], A) if n.nvec is None else
-                      policy_step_multi_supported(D, c["FC_DIM_SIZE"], c["GRU_HIDDEN_DIM"], n.nvec))
-                if not ok:
+                D = n.embed.in_features
+                if not policy_step_multi_supported(D, c["FC_DIM_SIZE"], c["GRU_HIDDEN_DIM"], n.heads):
                     raise ValueError(f"FUSED_POLICY needs GRU_HIDDEN_DIM and FC_DIM_SIZE in {list(SUPPORTED_HIDDEN)}, "
                                      f"an observation size <= {MAX_OBS_DIM} and <= {MAX_ACTIONS} actions (in each of "
                                      f"<= {MAX_HEADS} heads), got {c['GRU_HIDDEN_DIM']}, {c['FC_DIM_SIZE']}, {D} and "
-                                     f"{A if n.nvec is None else n.nvec} (agent type {i})")
+                                     f"{n.heads} (agent type {i})")
         # HIP-graph minibatch steps: single process on the GPU (the grad all-reduce stays eager)
         self.graphs = bool(c.get("CUDA_GRAPHS", False)) and self.device.type == "cuda" and world == 1
         if self.graphs:  # capturable Adam: step counter and lr live on the device
@@ -312,8 +314,7 @@ class IPPOTrainer:
         self.buf = [Rollout(obs=torch.empty((T, n, env.observation_spaces[i].shape[0]), device=self.device),
                             done=torch.empty((T, n), dtype=torch.bool, device=self.device),
                             global_done=torch.empty((T, n), dtype=torch.bool, device=self.device),
-                            action=torch.empty((T, n) if self.nets[i].nvec is None else (T, n, len(self.nets[i].nvec)),
-                                               dtype=torch.int32, device=self.device),
+                            action=torch.empty(self.nets[i].action_shape(T, n), dtype=torch.int32, device=self.device),
                             value=torch.empty((T, n), device=self.device),
                             reward=torch.empty((T, n), device=self.device),
                             log_prob=torch.empty((T, n), device=self.device))
@@ -362,35 +363,25 @@ class IPPOTrainer:
                 b = self.buf[i]
                 b.obs[t].copy_(self.last_obs[i])
                 b.done[t].copy_(self.last_done[i])
-                ashape = (self.E, self.n_agents[i]) if net.nvec is None else (self.E, self.n_agents[i], len(net.nvec))
+                # the env's view of the step's action words: [E, n] for a Discrete type, [E, n, K] otherwise
+                actions.append(b.action[t].view(net.action_shape(self.E, self.n_agents[i])))
                 if self.fused_policy:  # pol_rng, sub = split(pol_rng); one launch: carry in place, outputs into the buffers
                     k = self._split(self.pol_rng[None], 2)[0]
                     self.pol_rng.copy_(k[0])
-                    out = (b.action[t], b.log_prob[t], b.value[t])
-                    if net.nvec is None:
-                        policy_step(net, self.last_obs[i], self.last_done[i], self.h[i], SAMPLE, key=k[1], out=out)
-                    else:
-                        policy_step_multi(net, self.last_obs[i], self.last_done[i], self.h[i], SAMPLE, net.nvec,
-                                          key=k[1], out=out)
-                    actions.append(b.action[t].view(ashape))
+                    policy_step_net(net, self.last_obs[i], self.last_done[i], self.h[i], SAMPLE, key=k[1],
+                                    out=(b.action[t], b.log_prob[t], b.value[t]))
                     continue
                 h, logits, v = net.step(self.h[i], self.last_obs[i], self.last_done[i])
                 self.h[i].copy_(h)
                 b.value[t].copy_(v)
-                if net.nvec is not None:   # one draw per head, in head order; log_prob adds the heads'
-                    lp = 0.0
-                    for k, lg in enumerate(logits.split(net.nvec, -1)):
-                        a = torch.multinomial(torch.softmax(lg, -1), 1, generator=self.gen)
-                        b.action[t][:, k].copy_(a.squeeze(-1))
-                        lp = lp + torch.log_softmax(lg, -1).gather(-1, a).squeeze(-1)
-                    b.log_prob[t].copy_(lp)
-                    actions.append(b.action[t].view(ashape))
-                    continue
-                probs = torch.softmax(logits, -1)
-                a = torch.multinomial(probs, 1, generator=self.gen).squeeze(-1)
-                b.action[t].copy_(a)
-                b.log_prob[t].copy_(torch.log_softmax(logits, -1).gather(-1, a.unsqueeze(-1)).squeeze(-1))
-                actions.append(a.view(self.E, self.n_agents[i]))
+                # one draw per head, in head order; log_prob adds the heads' from the first one's
+                words = b.action[t].view(self.n_actors[i], len(net.heads))
+                for k, lg in enumerate(logits.split(net.heads, -1)):
+                    a = torch.multinomial(torch.softmax(lg, -1), 1, generator=self.gen)
+                    words[:, k].copy_(a.squeeze(-1))
+                    lpk = torch.log_softmax(lg, -1).gather(-1, a).squeeze(-1)
+                    lp = lpk if k == 0 else lp + lpk
+                b.log_prob[t].copy_(lp)
             obs, self.state, rew, dones, _ = self.env.step(self._next_keys(), self.state, actions, self.params)
             for i in range(self.n_types):
                 b = self.buf[i]
@@ -418,9 +409,9 @@ class IPPOTrainer:
         c, net, opt, b, st = self.c, self.nets[i], self.opts[i], self.buf[i], self._st[i]
         idx = st["idx"]
         logits, values = net(st["h0"][idx], b.obs[:, idx], b.done[:, idx])
-        args = (logits, values, b.action[:, idx], b.value[:, idx], b.log_prob[:, idx], st["adv"][:, idx],
-                st["tgt"][:, idx], c["CLIP_EPS"], c["VF_COEF"][i], c["ENT_COEF"][i])
-        out = ppo_loss(*args) if net.nvec is None else ppo_loss_multi(*args, net.nvec)
+        out = ppo_loss_multi(logits, values, b.action[:, idx].view(self.T, -1, len(net.heads)), b.value[:, idx],
+                             b.log_prob[:, idx], st["adv"][:, idx], st["tgt"][:, idx], c["CLIP_EPS"], c["VF_COEF"][i],
+                             c["ENT_COEF"][i], net.heads)
         out[0].backward()
         if self.dist is not None and self.dist.get_world_size() > 1:
             _average_grads(list(net.parameters()), self.dist)
@@ -496,8 +487,7 @@ class IPPOTrainer:
         torch.save({"format": CHECKPOINT_FORMAT, "nets": [n.state_dict() for n in self.nets],
                     "opts": [o.state_dict() for o in self.opts], "opt_count": list(self.opt_count),
                     "config": dict(self.c), "env_config": env_cfg,
-                    "shapes": [(n.embed.in_features, n.actor2.out_features if n.nvec is None else list(n.nvec))
-                               for n in self.nets]}, path)
+                    "shapes": [(n.embed.in_features, head_sizes(n.heads)) for n in self.nets]}, path)
 
     def load_checkpoint(self, path: str) -> None:
         """Restores what ``save_checkpoint`` wrote into this trainer (same env and sizes).  The

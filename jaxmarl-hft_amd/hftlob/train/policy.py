@@ -11,7 +11,9 @@ path: one HIP launch, used by the trainer's rollout (``FUSED_POLICY``) and by
 action space (``hftlob_policy_step_multi``): K categorical heads on the shared actor features
 (MultiActionOutputIndependant / MultiCategorical, :80-100, 259-281), the rows of ``actor2`` stacked
 head after head; head k samples with ``jax.random.split(key, K)[k]``, and one head is the
-single-head operator with the key unsplit, as the reference collapses a list of one.
+single-head operator with the key unsplit, as the reference collapses a list of one.  Both pairs
+are one body over a list of head widths; ``policy_step_net`` steps an ``ActorCriticRNN`` through
+the operator its heads need.
 
 Sampling (mode 0) is ``jax.random.categorical(key, logits)``: the first argmax of
 ``logits + g`` with ``g = jax.random.gumbel(key, (B, A))`` under the partitionable threefry
@@ -156,26 +158,11 @@ def _head_reference(logits, gumbel):
     return action, logp.gather(-1, action[:, None]).squeeze(-1)
 
 
-def policy_step_reference(net_or_weights, obs, done, h, mode: int, key=None, gumbel=None):
-    """hftlob_policy_step in torch, in the float type of ``obs`` (the weights are converted to
-    it): returns (h [B, H], logits [B, A], value [B], action int64 [B], log_prob [B]).  Mode 0
-    adds ``gumbel`` [B, A] to the logits before the argmax, or ``gumbel_noise(key, B, A)``."""
-    if mode not in (SAMPLE, GREEDY):
-        raise ValueError("mode must be 0 (sample) or 1 (argmax)")
-    hnew, logits, value = _trunk_reference(net_or_weights, obs, done, h)
-    if mode == SAMPLE and gumbel is None:
-        if key is None:
-            raise ValueError("mode 0 needs key or gumbel")
-        gumbel = gumbel_noise(key, logits.shape[0], logits.shape[1])
-    action, logp = _head_reference(logits, gumbel if mode == SAMPLE else None)
-    return hnew, logits, value, action, logp
-
-
 def policy_step_multi_reference(net_or_weights, obs, done, h, mode: int, nvec: Sequence[int], key=None, gumbel=None):
-    """hftlob_policy_step_multi in torch, in the float type of ``obs``: returns (h [B, H],
-    logits [B, S], value [B], action int64 [B, K], log_prob [B]).  Mode 0 adds ``gumbel[k]``
-    [B, nvec[k]] to head k's logits, or ``gumbel_noise(head_keys(key, K)[k], B, nvec[k])``;
-    log_prob adds the heads' log-probabilities in head order."""
+    """hftlob_policy_step_multi in torch, in the float type of ``obs`` (the weights are converted to
+    it): returns (h [B, H], logits [B, S], value [B], action int64 [B, K], log_prob [B]).  Mode 0
+    adds ``gumbel[k]`` [B, nvec[k]] to head k's logits, or ``gumbel_noise(head_keys(key, K)[k], B,
+    nvec[k])``; log_prob adds the heads' log-probabilities in head order."""
     if mode not in (SAMPLE, GREEDY):
         raise ValueError("mode must be 0 (sample) or 1 (argmax)")
     nvec = [int(n) for n in nvec]
@@ -194,6 +181,16 @@ def policy_step_multi_reference(net_or_weights, obs, done, h, mode: int, nvec: S
     return hnew, logits, value, torch.stack(actions, -1), logp
 
 
+def policy_step_reference(net_or_weights, obs, done, h, mode: int, key=None, gumbel=None):
+    """hftlob_policy_step in torch: ``policy_step_multi_reference`` with the one head of all A rows of
+    ``actor2`` (so the key is used unsplit), ``gumbel`` the head's [B, A] tensor, and the action
+    int64 [B]."""
+    A = net_weights(net_or_weights)["w_a2"].shape[0]
+    hnew, logits, value, action, logp = policy_step_multi_reference(
+        net_or_weights, obs, done, h, mode, [A], key=key, gumbel=None if gumbel is None else [gumbel])
+    return hnew, logits, value, action.squeeze(-1), logp
+
+
 # ------------------------------------------------------------------ the fused path
 def _weights_struct(W: Dict[str, torch.Tensor], D: int, FC: int, H: int, A: int) -> _lib.PolicyWeights:
     shapes = {"w_embed": (FC, D), "b_embed": (FC,), "w_ih": (3 * H, FC), "b_ih": (3 * H,), "w_hh": (3 * H, H),
@@ -208,25 +205,21 @@ def _weights_struct(W: Dict[str, torch.Tensor], D: int, FC: int, H: int, A: int)
     return s
 
 
-def _fused_call(op: str, net, obs, done, h, mode: int, nvec, key, out, h_out, logits: bool):
-    """The two operators' shared host side: shape checks, output allocation and the one launch.
-    nvec None is hftlob_policy_step (action [B], key [2]); a list is hftlob_policy_step_multi
-    (action [B, K], key [K, 2])."""
+def _fused_call(op: str, net, obs, done, h, mode: int, heads, flat: bool, key, out, h_out, logits: bool):
+    """The two operators' shared host side: shape checks, output allocation, the heads' keys and the
+    one launch, for the heads' widths ``heads`` over the rows of ``actor2``.  flat: the one head of
+    hftlob_policy_step, whose action is [B]; else hftlob_policy_step_multi's [B, K]."""
     W = net_weights(net)
     if obs.dim() != 2 or h.dim() != 2:
         raise ValueError(f"{op}: obs must be [B, D] and h [B, H]")
     B, D = obs.shape
-    H = h.shape[1]
+    H, K = h.shape[1], len(heads)
     FC, A = W["w_embed"].shape[0], W["w_a2"].shape[0]
-    if nvec is None:
-        ok, heads, ashape = policy_step_supported(D, FC, H, A), f"1..{MAX_ACTIONS} actions", (B,)
-    else:
-        ok = policy_step_multi_supported(D, FC, H, nvec) and sum(nvec) == A
-        heads, ashape = f"1..{MAX_HEADS} heads of 1..{MAX_ACTIONS} actions over the {A} rows of actor2", (B, len(nvec))
-    if not ok:
+    ashape = (B,) if flat else (B, K)
+    if not policy_step_multi_supported(D, FC, H, heads) or sum(heads) != A:
         raise ValueError(f"{op} needs GRU_HIDDEN_DIM and FC_DIM_SIZE in {list(SUPPORTED_HIDDEN)}, an obs size "
-                         f"in 1..{MAX_OBS_DIM} and {heads}, got H {H}, FC {FC}, D {D}, "
-                         + (f"A {A}" if nvec is None else f"nvec {list(nvec)}"))
+                         f"in 1..{MAX_OBS_DIM} and 1..{MAX_HEADS} heads of 1..{MAX_ACTIONS} actions over the {A} rows "
+                         f"of actor2, got H {H}, FC {FC}, D {D}, heads {heads}")
     if mode not in (SAMPLE, GREEDY):
         raise ValueError(f"{op}: mode must be 0 (sample) or 1 (argmax)")
     dev = obs.device
@@ -247,22 +240,20 @@ def _fused_call(op: str, net, obs, done, h, mode: int, nvec, key, out, h_out, lo
                              f"{list(t.shape)} on {t.device}")
     kp = None
     if mode == SAMPLE:
-        n_words = 2 if nvec is None else 2 * len(nvec)
-        if key is None or key.dtype not in (torch.int32, torch.uint32) or key.numel() != n_words or key.device != dev:
-            raise ValueError(f"{op}: mode 0 needs key, a uint32/int32 tensor of "
-                             + ("2 words" if nvec is None else f"[{len(nvec)}, 2] words (one key per head)") + f" on {dev}")
+        if key is None or key.dtype not in (torch.int32, torch.uint32) or key.numel() != 2 or key.device != dev:
+            raise ValueError(f"{op}: mode 0 needs key, a uint32/int32 tensor of 2 words on {dev}")
+        if K > 1:   # head_keys on the device: [K, 2], one more small launch (one head takes the key unsplit)
+            from ..env import split_keys
+            key = split_keys(key.reshape(1, 2), K)[0]
         kp = _lib.ptr(key)
     ws = _weights_struct(W, D, FC, H, A)
-    tail = (int(mode), kp, _lib.ptr(action), _lib.ptr(log_prob), _lib.ptr(value), _lib.ptr(lg),
-            _lib.stream_ptr(device=dev))
+    args = (C.byref(ws), _lib.ptr(obs), _lib.ptr(done), _lib.ptr(h), _lib.ptr(h_out), int(mode), kp, _lib.ptr(action),
+            _lib.ptr(log_prob), _lib.ptr(value), _lib.ptr(lg), _lib.stream_ptr(device=dev))
     with torch.cuda.device(dev):
-        if nvec is None:
-            rc = _lib.lib().hftlob_policy_step(B, D, FC, H, A, C.byref(ws), _lib.ptr(obs), _lib.ptr(done), _lib.ptr(h),
-                                               _lib.ptr(h_out), *tail)
+        if flat:
+            rc = _lib.lib().hftlob_policy_step(B, D, FC, H, A, *args)
         else:
-            nv = (C.c_int * len(nvec))(*nvec)
-            rc = _lib.lib().hftlob_policy_step_multi(B, D, FC, H, len(nvec), nv, C.byref(ws), _lib.ptr(obs),
-                                                     _lib.ptr(done), _lib.ptr(h), _lib.ptr(h_out), *tail)
+            rc = _lib.lib().hftlob_policy_step_multi(B, D, FC, H, K, (C.c_int * K)(*heads), *args)
         _lib.check(rc)
     return h_out, action, log_prob, value, lg
 
@@ -277,7 +268,8 @@ def policy_step(net, obs, done, h, mode: int, key=None, out=None, h_out=None, lo
     out: ``(action int32 [B], log_prob float32 [B], value float32 [B])`` to write into (for example
     rows of the rollout buffers); None allocates them.  h_out: where the new carry goes; None
     updates ``h`` in place.  Returns ``(h_out, action, log_prob, value, logits or None)``."""
-    return _fused_call("policy_step", net, obs, done, h, mode, None, key, out, h_out, logits)
+    heads = [net_weights(net)["w_a2"].shape[0]]   # one head of all the rows of actor2
+    return _fused_call("policy_step", net, obs, done, h, mode, heads, True, key, out, h_out, logits)
 
 
 def policy_step_multi(net, obs, done, h, mode: int, nvec: Sequence[int], key=None, out=None, h_out=None,
@@ -287,10 +279,14 @@ def policy_step_multi(net, obs, done, h, mode: int, nvec: Sequence[int], key=Non
     into the heads' K keys on the device here (``split_keys``, one more small launch; nothing
     synchronises), and passed through for one head.  ``action`` is int32 [B, K], ``logits``
     [B, sum(nvec)]; the rest is as for ``policy_step``."""
-    nvec = [int(n) for n in nvec]
-    if mode == SAMPLE and len(nvec) > 1:   # (one head: _fused_call checks the key it is handed)
-        if key is None or key.dtype not in (torch.int32, torch.uint32) or key.numel() != 2 or not key.is_cuda:
-            raise ValueError("policy_step_multi: mode 0 needs key, a uint32/int32 tensor of 2 words on the device")
-        from ..env import split_keys
-        key = split_keys(key.reshape(1, 2), len(nvec))[0]
-    return _fused_call("policy_step_multi", net, obs, done, h, mode, nvec, key, out, h_out, logits)
+    return _fused_call("policy_step_multi", net, obs, done, h, mode, [int(n) for n in nvec], False, key, out, h_out,
+                       logits)
+
+
+def policy_step_net(net, obs, done, h, mode: int, key=None, out=None):
+    """One step of an ``ActorCriticRNN`` through the operator its action space needs, the carry ``h``
+    updated in place: ``policy_step`` for a Discrete space (action [B]), ``policy_step_multi`` over
+    ``net.heads`` for a MultiDiscrete one (action [B, K]).  Returns what they return."""
+    flat = net.action_shape() == ()
+    return _fused_call("policy_step" if flat else "policy_step_multi", net, obs, done, h, mode, net.heads, flat, key,
+                       out, None, False)

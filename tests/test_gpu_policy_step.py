@@ -19,9 +19,11 @@ pytestmark = pytest.mark.gpu
 
 # (B, D, FC, H, A, every row done): one row, D no multiple of 4; exactly one tile; a second tile with
 # one live row, FC != H; H > FC and a full action block; the learner's sizes, every k loop at full
-# length; that again with every carry reset
+# length; that again with every carry reset; a head of one logit (action 0, log-prob exactly 0), one
+# tile plus one row at the smallest D and the smallest kernel
 CASES = [(1, 3, 64, 64, 2, False), (16, 6, 64, 64, 5, False), (17, 13, 128, 64, 10, False),
-         (33, 16, 64, 128, 16, False), (40, 9, 256, 256, 9, False), (40, 9, 256, 256, 9, True)]
+         (33, 16, 64, 128, 16, False), (40, 9, 256, 256, 9, False), (40, 9, 256, 256, 9, True),
+         (17, 1, 64, 64, 1, False)]
 TILE = 16
 GAP = 1e-3
 
@@ -40,6 +42,8 @@ def assert_close(name, got, ref):
 
 
 def top_two_gap(score):
+    if score.shape[-1] < 2:                                            # a one-logit head has no second
+        return float("inf")
     top = score.double().topk(2, dim=-1).values
     return float((top[:, 0] - top[:, 1]).min())
 
@@ -86,6 +90,8 @@ def test_outputs_match_float64(B, D, FC, H, A, all_done):
     assert_close("value", value, ref["value"])
     assert action.dtype == torch.int32 and torch.equal(action.cpu().long(), ref["action"])
     assert_close("log_prob", log_prob, ref["log_prob"])
+    if A == 1:
+        assert not bool(action.any()) and bool((log_prob == 0.0).all())
     assert torch.equal(c["h"].cpu(), x["h"])                           # h_in is not touched when h_out is given
     if all_done:                                                       # the carry plays no part
         other = P.policy_step(Wd, c["obs"], c["done"], torch.full_like(c["h"], 7.0), P.GREEDY, logits=True)
@@ -104,7 +110,7 @@ def test_exact_ties_take_the_first(B, D, FC, H, A, all_done):
     assert out[1].tolist() == [1] * B
 
 
-@pytest.mark.parametrize("B,D,FC,H,A,all_done", CASES[:5])
+@pytest.mark.parametrize("B,D,FC,H,A,all_done", CASES[:5] + CASES[6:])
 def test_sampling_is_the_gumbel_argmax(B, D, FC, H, A, all_done):
     W, x, ref = case(B, D, FC, H, A, all_done)
     k = 0
@@ -121,6 +127,8 @@ def test_sampling_is_the_gumbel_argmax(B, D, FC, H, A, all_done):
     assert torch.equal(action.cpu().long(), want)                      # every row
     assert_close("log_prob", log_prob, torch.log_softmax(lg, -1).gather(-1, want[:, None]).squeeze(-1))
     assert_close("value", value, ref["value"])
+    if A == 1:
+        assert not bool(action.any()) and bool((log_prob == 0.0).all())
     if B == 40:
         other = P.policy_step(Wd, c["obs"], c["done"], c["h"].clone(), P.SAMPLE, key=key_tensor(k + 1))[1]
         assert not torch.equal(other, action)
