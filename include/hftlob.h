@@ -414,6 +414,32 @@ int hftlob_env_rollout_eval(const hftlob_env_cfg* cfg /*[host]*/, int n_env, int
                             const int32_t* init_states, int32_t* state, double* stats,
                             const hftlob_step_out* out /*[host] struct*/, void* stream);
 
+/* The accumulators above from per-step outputs, as one launch — replaces the reduction of the
+ * trajectory batch in baseline_eval/baseline_JAXMARL.py (:819-951) for a caller whose actions do not
+ * come from the env launch (a policy network: hftlob/evaluate.py evaluate_policy), and who therefore
+ * holds each step's rewards, info record and global dones.
+ * rewards float [n_steps][n_env][n_agents]; info int32 [n_steps][n_env][info_words], the raw record
+ * of hftlob_step_out.info, agent a's words from HFTLOB_INFO_WORLD_WORDS + a * HFTLOB_INFO_AGENT_WORDS;
+ * done_all bytes [n_steps][n_env] (non-zero: the step ended the env's episode).
+ * float_words uint32 [n_agents], HOST: bit k set = info word k of that agent is a float, widened
+ * float -> double; a clear bit widens the word int32 -> double (hftlob/evaluate.py _float_words gives
+ * the map of a layout).  The array is read at the call and travels to the kernel by value.
+ * stats double [n_env][n_agents][HFTLOB_EVAL_WORDS], in/out: the call ADDS the n_steps steps in order
+ * to what it finds, the words as listed for hftlob_env_rollout_eval, every one a plain sequential
+ * double sum of separately rounded terms (no fused multiply-add), so the result is bit for bit
+ * hftlob/evaluate.py reduce_steps and, over the same steps, the stats of hftlob_env_rollout_eval; a
+ * run cut into calls gives the bits of one call.
+ * One lane per (env, agent, quantity): each stats word is read once and written once per launch;
+ * no LDS, no atomics.  The call neither allocates nor synchronises and can be captured in a hipGraph.
+ * HFTLOB_EINVAL: a NULL pointer; n_env, n_agents or n_steps < 1; n_agents > HFTLOB_MAX_AGENTS;
+ * info_words < HFTLOB_INFO_WORLD_WORDS + n_agents * HFTLOB_INFO_AGENT_WORDS. */
+int hftlob_eval_tally(int n_env, int n_agents, int n_steps, int info_words,
+                      const float* rewards /*[n_steps][n_env][n_agents]*/,
+                      const int32_t* info /*[n_steps][n_env][info_words]*/,
+                      const uint8_t* done_all /*[n_steps][n_env]*/,
+                      const uint32_t* float_words /*[n_agents], host*/,
+                      double* stats /*[n_env][n_agents][HFTLOB_EVAL_WORDS], in/out*/, void* stream);
+
 /* Creates the library streams / events hftlob_env_rollout_sampled needs for n_slices
  * slices on the device of `stream` (host-only; idempotent). */
 int hftlob_rollout_prepare(int n_slices, void* stream);

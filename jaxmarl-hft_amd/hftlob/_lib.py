@@ -30,7 +30,7 @@ EVAL_WORDS = 106  # HFTLOB_EVAL_WORDS: doubles per agent in hftlob_env_rollout_e
 EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob_book_depth",
            "hftlob_book_process_depth", "hftlob_env_reset",
            "hftlob_env_step", "hftlob_env_step_sampled", "hftlob_env_rollout_sampled", "hftlob_rollout_prepare",
-           "hftlob_env_rollout_actions", "hftlob_env_rollout_eval",
+           "hftlob_env_rollout_actions", "hftlob_env_rollout_eval", "hftlob_eval_tally",
            "hftlob_env_lds_bytes", "hftlob_env_launch_info", "hftlob_env_baked_id", "hftlob_set_baked",
            "hftlob_sample_actions", "hftlob_split_keys", "hftlob_gru_scan_fwd", "hftlob_gru_scan_bwd",
            "hftlob_policy_step", "hftlob_policy_step_multi")
@@ -73,6 +73,8 @@ def lib() -> C.CDLL:
     L.hftlob_env_rollout_actions.restype = i32
     L.hftlob_env_rollout_eval.argtypes = [C.POINTER(EnvCfg), i32, i32, vp, vp, i32, vp, vp, vp, vp, C.POINTER(StepOut), vp]
     L.hftlob_env_rollout_eval.restype = i32
+    L.hftlob_eval_tally.argtypes = [i32, i32, i32, i32, vp, vp, vp, C.POINTER(C.c_uint32), vp, vp]
+    L.hftlob_eval_tally.restype = i32
     L.hftlob_rollout_prepare.argtypes = [i32, vp]
     L.hftlob_rollout_prepare.restype = i32
     L.hftlob_env_lds_bytes.argtypes = [C.POINTER(EnvCfg)]

@@ -677,6 +677,7 @@ class MARLEnv:
 
     def _results(self, o, state, E):
         self.last_info_words = o["info"]  # raw info record of the last step (int32 [E, info_words]) or None
+        self.last_rewards = o["rewards"]  # the last step's rewards as the launch wrote them (float32 [E, num_agents])
         obs, a = self._split_types(o["obs"], True), 0
         for t, n_t in enumerate(self.multi_agent_config.number_of_agents_per_type):
             obs[t] = self._message_obs(o, obs[t], t, a, n_t, E)

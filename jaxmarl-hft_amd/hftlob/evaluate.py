@@ -11,16 +11,24 @@ into per-agent accumulators instead of writing a trajectory.
   into counts, means and population standard deviations per agent type.
 * :func:`evaluate_fixed_actions` is the script's loop; ``python -m hftlob.evaluate`` prints its
   numbers as one JSON object.
+* :func:`tally_steps` is :func:`reduce_steps` as one HIP launch (hftlob_eval_tally), bit for bit.
 * :func:`evaluate_policy` is the same loop with the recurrent policies of a checkpoint
-  (``hftlob.train.ippo.load_policy``) in place of the fixed actions: one fused policy step per agent
-  type and one env step per step, reduced with :func:`reduce_steps`
+  (``hftlob.train.ippo.load_policy``) in place of the fixed actions, for all agent types or, with a
+  fixed action for the others, for some: one fused policy step per learned type and one env step per
+  step, each step tallied from the env's output buffers with :func:`tally_steps`
   (``python -m hftlob.evaluate --checkpoint PATH``).
+* :func:`evaluate_combinations` runs every learned / baseline mix per agent type under one seed, the
+  reference's baseline_eval/baseline_JAXMARL.py (``BB``, ``BL``, ``LB``, ``LL`` for two types;
+  ``--checkpoint PATH --baseline-actions 4,2 --combinations``).  The reference's per-combination
+  agent-config overrides (BASELINE_CONFIGS, get_ma_config) are not covered: one env config serves
+  every combination.
 
 Plotting (the rest of baseline_eval/) is not covered.
 """
 from __future__ import annotations
 
 import argparse
+import ctypes as C
 import json
 import math
 import os
@@ -29,6 +37,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
+from . import _lib
 from ._lib import EVAL_WORDS
 from .layout import AGENT_MM, INFO_AGENT_WORDS, INFO_EXE, INFO_MM, INFO_WORLD_WORDS
 
@@ -100,6 +109,59 @@ def reduce_steps(rewards, info_words: torch.Tensor, done_all: torch.Tensor, layo
         st[:, :, W_END_INFO + 1::2] = torch.where(d3, st[:, :, W_END_INFO + 1::2] + x2[t, :, :, 1:],
                                                   st[:, :, W_END_INFO + 1::2])
     return st
+
+
+def _float_word_masks(layout):
+    """:func:`_float_words` as hftlob_eval_tally's host array: uint32 [n_agents], bit k = word k is a float"""
+    rows = _float_words(layout).tolist()
+    return (C.c_uint32 * len(rows))(*[sum(1 << k for k, isf in enumerate(r) if isf) for r in rows])
+
+
+def _tally_launch(rewards, info_words, done_all, masks, info_w: int, stats) -> None:
+    """hftlob_eval_tally on checked device tensors ([T, E, A], [T, E, info_w], [T, E] bytes), adding to stats"""
+    T, E, A = rewards.shape
+    dev = rewards.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().hftlob_eval_tally(E, A, T, info_w, _lib.ptr(rewards), _lib.ptr(info_words),
+                                                _lib.ptr(done_all), masks, _lib.ptr(stats),
+                                                _lib.stream_ptr(device=dev)))
+
+
+def tally_steps(rewards, info_words: torch.Tensor, done_all: torch.Tensor, layout,
+                stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`reduce_steps` as one launch of hftlob_eval_tally (csrc/eval_tally.hip) on torch's current
+    stream: the same arguments, the same bits.  The tensors must be on a GPU (there is no other path);
+    done_all is bool or uint8 [T, E].  Unlike reduce_steps a given ``stats`` (contiguous float64
+    [E, n_agents, EVAL_WORDS] on that device) is continued IN PLACE; None starts from zeros.  Returns
+    the stats tensor.  Nothing is allocated beyond a missing ``stats`` and a per-type rewards list's
+    concatenation, and nothing synchronises."""
+    if not isinstance(rewards, torch.Tensor):
+        rewards = torch.cat([x.reshape(x.shape[0], x.shape[1], -1) for x in rewards], dim=2)
+    if rewards.dim() != 3 or rewards.shape[2] != len(layout.agent_kinds) or rewards.dtype != torch.float32:
+        raise ValueError(f"rewards must be float32 [T, E, {len(layout.agent_kinds)}]")
+    T, E, A = rewards.shape
+    if T < 1 or E < 1:
+        raise ValueError("tally_steps needs at least one step and one env")
+    if not isinstance(info_words, torch.Tensor) or info_words.dtype != torch.int32 \
+            or info_words.numel() != T * E * layout.info_words:
+        raise ValueError(f"info_words must be int32 [T, E, {layout.info_words}]")
+    if not isinstance(done_all, torch.Tensor) or tuple(done_all.shape) != (T, E) \
+            or done_all.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("done_all must be bool or uint8 [T, E]")
+    dev = rewards.device
+    if dev.type != "cuda" or info_words.device != dev or done_all.device != dev:
+        raise ValueError(f"tally_steps needs its tensors on one GPU device, got {dev}, {info_words.device} and "
+                         f"{done_all.device}")
+    if stats is None:
+        stats = torch.zeros((E, A, EVAL_WORDS), dtype=torch.float64, device=dev)
+    elif (not isinstance(stats, torch.Tensor) or tuple(stats.shape) != (E, A, EVAL_WORDS) or stats.dtype != torch.float64
+          or stats.device != dev or not stats.is_contiguous()):
+        raise ValueError(f"stats must be a contiguous float64 [{E}, {A}, {EVAL_WORDS}] tensor on {dev}")
+    if done_all.dtype == torch.bool:
+        done_all = done_all.view(torch.uint8)
+    _tally_launch(rewards.contiguous(), info_words.contiguous(), done_all.contiguous(), _float_word_masks(layout),
+                  layout.info_words, stats)
+    return stats
 
 
 def _mean_std(n: float, s: float, s2: float) -> Dict[str, float]:
@@ -243,17 +305,44 @@ def evaluate_fixed_actions(env, fixed_actions: Sequence, n_envs: int, n_steps: i
     return EvalStats(stats, env.layout)
 
 
+def _fixed_action(t: int, a) -> int:
+    """one type's fixed action as :func:`fixed_action_row` reads it: an int, or a list of one int"""
+    if isinstance(a, (list, tuple)):
+        if len(a) != 1:
+            raise NotImplementedError(
+                f"agent type {t}: {len(a)} fixed actions; the reference draws one of them uniformly per step "
+                "(JAX's categorical), which is not implemented: give one action per agent type")
+        a = a[0]
+    if isinstance(a, bool) or not isinstance(a, int):
+        raise TypeError(f"agent type {t}: a policy entry must be an ActorCriticRNN, an int or a list of one int, "
+                        f"got {type(a).__name__}")
+    return a
+
+
+def policy_entries(nets: Sequence, n_types: int) -> list:
+    """The entries of :func:`evaluate_policy`'s ``nets`` checked, one per agent type: a network (any
+    ``torch.nn.Module``; an ``ActorCriticRNN`` is what runs) stays, a fixed action (an int, or a list
+    of one int as the reference's FIXED_ACTIONS writes it) becomes its int.  Host-only."""
+    if len(nets) != n_types:
+        raise ValueError(f"nets must hold one network or fixed action per agent type ({n_types}), got {len(nets)}")
+    return [p if isinstance(p, torch.nn.Module) else _fixed_action(t, p) for t, p in enumerate(nets)]
+
+
 def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: bool = True,
                     chunk: int = 64) -> EvalStats:
     """:func:`evaluate_fixed_actions` with recurrent policies in place of the fixed actions: ``nets``
-    holds one ``ActorCriticRNN`` per agent type (``hftlob.train.ippo.load_policy``).  The reset and
-    the env step keys are that function's chain unchanged; the key its chain leaves unused each step
-    (:func:`eval_keys`' "unused action sample") is the step's policy key, split once more per agent
-    type.  Each step is one fused policy step per type (``train.policy.policy_step_net``: the argmax
-    if ``greedy``, else a ``jax.random.categorical`` sample per head), followed by ``env.step``; the
-    carries start at zero and are reset by each actor's done.  The rewards, raw info words and global
-    dones of ``chunk`` steps are kept and reduced with :func:`reduce_steps`, the stats carried from
-    chunk to chunk.  The env must be built with ``return_info=True``."""
+    holds one entry per agent type, an ``ActorCriticRNN`` (``hftlob.train.ippo.load_policy``) or a
+    fixed action (an int, or a list of one int), in any mix.  Every agent of a fixed type, and every
+    action word of a MultiDiscrete one, takes that action at every step; the type has no carry and no
+    policy launch.  The reset and the env step keys are that function's chain unchanged; the key its
+    chain leaves unused each step (:func:`eval_keys`' "unused action sample") is the step's policy key,
+    split once more per agent type whatever the mix, so a learned type draws the same samples
+    whichever other types are fixed.  Each step is one fused policy step per learned type
+    (``train.policy.policy_step_net``: the argmax if ``greedy``, else a ``jax.random.categorical``
+    sample per head), followed by ``env.step`` and one :func:`tally_steps` launch over the env's own
+    output buffers (rewards, raw info words, global dones): nothing is copied or kept per step.  The
+    carries start at zero and are reset by each actor's done.  ``chunk`` sizes the key generation
+    only.  The env must be built with ``return_info=True``."""
     from .env import split_keys
     from .train.policy import GREEDY, SAMPLE, policy_step_net
     if n_envs < 1 or n_steps < 1 or chunk < 1:
@@ -261,8 +350,8 @@ def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: boo
     if not getattr(env, "return_info", False):
         raise ValueError("evaluate_policy reduces the steps' info words: build the env with return_info=True")
     counts = list(env.multi_agent_config.number_of_agents_per_type)
-    if len(nets) != len(counts):
-        raise ValueError(f"nets must hold one network per agent type ({len(counts)}), got {len(nets)}")
+    pols = policy_entries(nets, len(counts))
+    learned = [i for i, p in enumerate(pols) if not isinstance(p, int)]
     part = bool(env.cfg_c.prng_partitionable)
     params, dev, E, L = env.default_params, env.device, n_envs, env.layout
     mode = GREEDY if greedy else SAMPLE
@@ -271,32 +360,64 @@ def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: boo
     rng = pair[:, 0].contiguous()
     obs, state = env.reset(split_keys(pair[:, 1].contiguous(), n_envs, part)[0], params)
     n_act = [n * E for n in counts]
-    obs = [o.reshape(n, -1).contiguous() for o, n in zip(obs, n_act)]
-    done = [torch.zeros(n, dtype=torch.bool, device=dev) for n in n_act]
-    h = [torch.zeros(n, net.hidden, device=dev) for n, net in zip(n_act, nets)]
-    stats = None
+    # a fixed type's action words, built once: [E, n_t * width]
+    actions = [torch.full((E, n * wd), p, dtype=torch.int32, device=dev) if isinstance(p, int) else None
+               for p, n, wd in zip(pols, counts, env.action_widths)]
+    obs = {i: obs[i].reshape(n_act[i], -1).contiguous() for i in learned}
+    done = {i: torch.zeros(n_act[i], dtype=torch.bool, device=dev) for i in learned}
+    h = {i: torch.zeros(n_act[i], pols[i].hidden, device=dev) for i in learned}
+    masks = _float_word_masks(L)
+    A = len(L.agent_kinds)
+    stats = torch.zeros((E, A, EVAL_WORDS), dtype=torch.float64, device=dev)
     for t0 in range(0, n_steps, chunk):
         T = min(chunk, n_steps - t0)
         rng, sub, act = _key_chain(rng, T, part)
         keys = split_keys(torch.cat(sub).contiguous(), n_envs, part)                       # [T, E, 2]
-        pol = split_keys(torch.cat(act).contiguous(), len(nets), part)                     # [T, n_types, 2]
-        rew = [torch.empty((T, E, n), dtype=torch.float32, device=dev) for n in counts]
-        info = torch.empty((T, E, L.info_words), dtype=torch.int32, device=dev)
-        done_all = torch.empty((T, E), dtype=torch.bool, device=dev)
+        pol = split_keys(torch.cat(act).contiguous(), len(pols), part)                     # [T, n_types, 2]
         for t in range(T):
-            actions = []
-            for i, net in enumerate(nets):
-                a = policy_step_net(net, obs[i], done[i], h[i], mode, key=pol[t, i] if mode == SAMPLE else None)[1]
-                actions.append(a.view(E, counts[i], *a.shape[1:]))   # [E, n_t], or [E, n_t, K] of a MultiDiscrete type
-            o, state, r, d, _ = env.step(keys[t], state, actions, params)
-            info[t].copy_(env.last_info_words)
-            done_all[t].copy_(d["__all__"])
-            for i, n in enumerate(n_act):
-                rew[i][t].copy_(r[i].reshape(E, counts[i]))
-                obs[i] = o[i].reshape(n, -1).contiguous()
+            for i in learned:
+                a = policy_step_net(pols[i], obs[i], done[i], h[i], mode, key=pol[t, i] if mode == SAMPLE else None)[1]
+                actions[i] = a.view(E, counts[i], *a.shape[1:])   # [E, n_t], or [E, n_t, K] of a MultiDiscrete type
+            o, state, _, d, _ = env.step(keys[t], state, actions, params)
+            # the step's raw outputs where the env launch wrote them: [E, A], [E, info_words], [E]
+            _tally_launch(env.last_rewards.view(1, E, A), env.last_info_words.view(1, E, L.info_words),
+                          d["__all__"].view(torch.uint8).view(1, E), masks, L.info_words, stats)
+            for i in learned:
+                obs[i] = o[i].reshape(n_act[i], -1).contiguous()
                 done[i] = d["agents"][i].reshape(-1).contiguous()
-        stats = reduce_steps(rew, info, done_all, L, stats)
     return EvalStats(stats, L)
+
+
+def combination_names(n_types: int) -> List[str]:
+    """The reference's names of the 2^n learned / baseline mixes in its order (binary counting, one
+    character per agent type, 'L' for 1 and 'B' for 0): BB, BL, LB, LL for two types."""
+    if n_types < 1:
+        raise ValueError("n_types must be >= 1")
+    return ["".join("L" if (c >> (n_types - 1 - t)) & 1 else "B" for t in range(n_types)) for c in range(2 ** n_types)]
+
+
+def mix_entries(desc: str, nets: Sequence, fixed_actions: Sequence) -> list:
+    """:func:`evaluate_policy`'s ``nets`` of one mix: type t's network where ``desc[t]`` is 'L', its
+    fixed action where it is 'B'."""
+    if len(desc) != len(nets) or len(desc) != len(fixed_actions) or set(desc) - set("LB"):
+        raise ValueError(f"a mix is one 'L' or 'B' per agent type ({len(nets)} nets, {len(fixed_actions)} fixed "
+                         f"actions), got {desc!r}")
+    return [n if c == "L" else a for c, n, a in zip(desc, nets, fixed_actions)]
+
+
+def evaluate_combinations(env, nets, fixed_actions: Sequence, n_envs: int, n_steps: int, seed: int,
+                          greedy: bool = True) -> Dict[str, EvalStats]:
+    """baseline_JAXMARL.py's evaluation (:819-951): every combination of the learned policy
+    (``nets[t]``) and the baseline (``fixed_actions[t]``) per agent type through
+    :func:`evaluate_policy`, all under the same seed, so the runs are paired as the reference's are
+    (it passes the same rng to each).  Returns {name: EvalStats} in :func:`combination_names`' order.
+    One env config serves all combinations (the reference's per-combination agent configs are not
+    covered)."""
+    n = len(env.multi_agent_config.number_of_agents_per_type)
+    policy_entries(nets, n)
+    policy_entries(fixed_actions, n)
+    return {desc: evaluate_policy(env, mix_entries(desc, nets, fixed_actions), n_envs, n_steps, seed, greedy=greedy)
+            for desc in combination_names(n)}
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -309,11 +430,17 @@ def build_parser() -> argparse.ArgumentParser:
                       help="evaluate the policies of an IPPOTrainer checkpoint (python -m hftlob.train.ippo --save)")
     ap.add_argument("--sample", action="store_true",
                     help="with --checkpoint: sample the actions (jax.random.categorical) instead of the argmax")
+    ap.add_argument("--baseline-actions", metavar="A,B",
+                    help="with --checkpoint: one fixed action per agent type for the types a mix runs as baseline")
+    ap.add_argument("--combinations", action="store_true",
+                    help="with --baseline-actions: every learned / baseline mix per agent type (BB, BL, LB, LL)")
+    ap.add_argument("--mix", metavar="LB",
+                    help="with --baseline-actions: one mix, 'L' (learned) or 'B' (baseline) per agent type")
     ap.add_argument("--envs", type=int, required=True)
     ap.add_argument("--steps", type=int, required=True)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--chunk", type=int, default=None,
-                    help="steps per launch (default 256), or with --checkpoint per reduction (default 64)")
+                    help="steps per launch (default 256), or with --checkpoint per key generation (default 64)")
     ap.add_argument("--data-msgs", type=int, default=400_000, help="length of the synthetic message day")
     ap.add_argument("--device", default="cuda:0")
     return ap
@@ -324,6 +451,12 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if args.sample and not args.checkpoint:
         ap.error("--sample needs --checkpoint")
+    if args.baseline_actions and not args.checkpoint:
+        ap.error("--baseline-actions needs --checkpoint")
+    if (args.combinations or args.mix) and not args.baseline_actions:
+        ap.error("--combinations and --mix need --baseline-actions")
+    if args.baseline_actions and bool(args.combinations) == bool(args.mix):
+        ap.error("--baseline-actions takes one of --combinations and --mix")
     from .config_io import builtin_config, load_config_from_file
     from .data.synthetic import generate_day
     from .env import MARLEnv
@@ -334,6 +467,18 @@ def main(argv=None) -> int:
         from .train.ippo import load_policy
         env = MARLEnv(None, cfg, data=day, device=args.device, return_info=True, persistent_outputs=True)
         nets = load_policy(args.checkpoint, env, args.device)
+        if args.baseline_actions:
+            base = [int(x) for x in args.baseline_actions.split(",")]
+            out = {"env_config": args.env_config, "checkpoint": args.checkpoint, "sample": bool(args.sample),
+                   "baseline_actions": base, "envs": args.envs, "steps": args.steps, "seed": args.seed}
+            if args.combinations:
+                evs = evaluate_combinations(env, nets, base, args.envs, args.steps, args.seed, greedy=not args.sample)
+            else:
+                evs = {args.mix: evaluate_policy(env, mix_entries(args.mix, nets, base), args.envs, args.steps,
+                                                 args.seed, greedy=not args.sample, chunk=args.chunk or 64)}
+            out["combinations"] = {desc: ev.summary() for desc, ev in evs.items()}
+            print(json.dumps(out))
+            return 0
         ev = evaluate_policy(env, nets, args.envs, args.steps, args.seed, greedy=not args.sample,
                              chunk=args.chunk or 64)
         out = {"env_config": args.env_config, "checkpoint": args.checkpoint, "sample": bool(args.sample),

@@ -63,7 +63,8 @@ def default_config(**kw) -> Dict:
          "TOTAL_TIMESTEPS": 5e8, "UPDATE_EPOCHS": 4, "NUM_MINIBATCHES": 4, "GAMMA": [0.999999999, 0.999],
          "GAE_LAMBDA": [0.85, 0.9], "CLIP_EPS": 0.2, "ENT_COEF": [0.01, 0.01], "VF_COEF": [0.5, 0.5],
          "MAX_GRAD_NORM": [0.5, 0.5], "ANNEAL_LR": [True, True], "NUM_AGENTS_PER_TYPE": [1, 1], "SEED": 2,
-         "CUDA_GRAPHS": True, "FUSED_GRU": False, "FUSED_POLICY": False}
+         "CUDA_GRAPHS": True, "FUSED_GRU": False, "FUSED_POLICY": False,
+         "CALC_EVAL": False, "NUM_STEPS_EVAL": None}   # NUM_STEPS_EVAL None: NUM_STEPS
     c.update(kw)
     return c
 
@@ -228,8 +229,8 @@ def _average_grads(params, dist) -> None:
 class IPPOTrainer:
     """make_train(config)(rng) of the reference, one ``update`` per call."""
 
-    def __init__(self, env: MARLEnv, config: Dict, dist=None, device=None):
-        self.env, self.c, self.dist = env, config, dist
+    def __init__(self, env: MARLEnv, config: Dict, dist=None, device=None, eval_env: Optional[MARLEnv] = None):
+        self.env, self.c, self.dist, self.eval_env = env, config, dist, eval_env
         self.device = torch.device(device or env.device)
         nt = len(env.list_of_agents_configs)
         self.n_types = nt
@@ -277,6 +278,25 @@ class IPPOTrainer:
                                      f"an observation size <= {MAX_OBS_DIM} and <= {MAX_ACTIONS} actions (in each of "
                                      f"<= {MAX_HEADS} heads), got {c['GRU_HIDDEN_DIM']}, {c['FC_DIM_SIZE']}, {D} and "
                                      f"{n.heads} (agent type {i})")
+        # CALC_EVAL (:461-482, 876-975): after every update NUM_STEPS_EVAL sampled steps of the current nets
+        # in a separate eval env, through the fused policy step and the tally launch (evaluate_policy)
+        self.calc_eval = bool(c.get("CALC_EVAL", False))
+        self.updates_done = 0
+        if self.calc_eval:
+            self.T_eval = int(c.get("NUM_STEPS_EVAL") or self.T)
+            if self.T_eval < 1:
+                raise ValueError(f"NUM_STEPS_EVAL must be >= 1, got {self.T_eval}")
+            if eval_env is None or not getattr(eval_env, "return_info", False):
+                raise ValueError("CALC_EVAL needs eval_env, a second MARLEnv built with return_info=True")
+            if self.device.type != "cuda":
+                raise ValueError(f"CALC_EVAL needs a GPU device, got {self.device}")
+            for i, n in enumerate(self.nets):
+                if not policy_step_multi_supported(n.embed.in_features, c["FC_DIM_SIZE"], c["GRU_HIDDEN_DIM"], n.heads):
+                    raise ValueError(f"CALC_EVAL runs the fused policy step: it needs GRU_HIDDEN_DIM and FC_DIM_SIZE in "
+                                     f"{list(SUPPORTED_HIDDEN)}, an observation size <= {MAX_OBS_DIM} and <= "
+                                     f"{MAX_ACTIONS} actions (in each of <= {MAX_HEADS} heads), got "
+                                     f"{c['GRU_HIDDEN_DIM']}, {c['FC_DIM_SIZE']}, {n.embed.in_features} and {n.heads} "
+                                     f"(agent type {i})")
         # HIP-graph minibatch steps: single process on the GPU (the grad all-reduce stays eager)
         self.graphs = bool(c.get("CUDA_GRAPHS", False)) and self.device.type == "cuda" and world == 1
         if self.graphs:  # capturable Adam: step counter and lr live on the device
@@ -475,7 +495,33 @@ class IPPOTrainer:
             metrics["loss"].append(dict(zip(("total_loss", "value_loss", "actor_loss", "entropy", "approx_kl",
                                              "clip_frac"), stats)))
             metrics["avg_reward"].append(b.reward.mean())
+        if self.calc_eval:
+            ev = self.evaluate(self.updates_done)
+            metrics["eval"] = ev
+            metrics["avg_reward_eval"] = [ev.reward(i)["mean"] for i in range(self.n_types)]
+        self.updates_done += 1
         return metrics
+
+    def eval_seed(self, update: int) -> int:
+        """The seed of the evaluation after update number ``update`` (0 the first), from a key no other
+        chain uses: word 0 of threefry2x32 under the key (words "evl", SEED) at the counter (rank,
+        update), jax.random.fold_in's form.  Computed on the host: it reads no key the training carries."""
+        import numpy as np
+        from .policy import threefry2x32
+        rank = self.dist.get_rank() if self.dist is not None else 0
+        y0, _ = threefry2x32(0x65766C, int(self.c["SEED"]) & 0xFFFFFFFF, np.array([rank], np.uint32),
+                             np.array([update & 0xFFFFFFFF], np.uint32))
+        return int(y0[0])
+
+    @torch.no_grad()
+    def evaluate(self, update: int):
+        """The reference's CALC_EVAL block (:943-975): a fresh reset of ``eval_env``, zero carries and
+        NUM_STEPS_EVAL sampled steps of the current nets for this rank's envs, as
+        ``evaluate_policy(eval_env, nets, E, NUM_STEPS_EVAL, eval_seed(update), greedy=False)``.  It runs
+        eagerly, outside the captured graphs, and touches neither ``rng``, ``pol_rng`` nor torch's
+        generator, so a run with CALC_EVAL trains bit for bit as one without."""
+        from ..evaluate import evaluate_policy
+        return evaluate_policy(self.eval_env, self.nets, self.E, self.T_eval, self.eval_seed(update), greedy=False)
 
     # ------------------------------------------------------------------ checkpoints
     def save_checkpoint(self, path: str) -> None:
@@ -539,9 +585,10 @@ def load_policy(path: str, env=None, device=None) -> List[ActorCriticRNN]:
     return nets
 
 
-def train(env: MARLEnv, config: Dict, n_updates: Optional[int] = None, dist=None, log=print):
-    """Runs ``n_updates`` (default NUM_UPDATES) updates; returns (trainer, env-steps/s over the run)."""
-    tr = IPPOTrainer(env, config, dist=dist)
+def train(env: MARLEnv, config: Dict, n_updates: Optional[int] = None, dist=None, log=print, eval_env=None):
+    """Runs ``n_updates`` (default NUM_UPDATES) updates; returns (trainer, env-steps/s over the run, the
+    CALC_EVAL steps in ``eval_env`` not counted)."""
+    tr = IPPOTrainer(env, config, dist=dist, eval_env=eval_env)
     n = n_updates or tr.num_updates
     sync = torch.cuda.synchronize if tr.device.type == "cuda" else (lambda: None)
     sync()
@@ -549,8 +596,11 @@ def train(env: MARLEnv, config: Dict, n_updates: Optional[int] = None, dist=None
     for u in range(n):
         m = tr.update()
         if log is not None:
-            log({"update": u, "avg_reward": [float(r) for r in m["avg_reward"]],
-                 "loss": [{k: float(v) for k, v in d.items()} for d in m["loss"]]})
+            rec = {"update": u, "avg_reward": [float(r) for r in m["avg_reward"]],
+                   "loss": [{k: float(v) for k, v in d.items()} for d in m["loss"]]}
+            if "avg_reward_eval" in m:
+                rec["avg_reward_eval"] = [float(r) for r in m["avg_reward_eval"]]
+            log(rec)
     sync()
     world = dist.get_world_size() if dist is not None else 1
     return tr, n * tr.T * tr.E * world / (time.perf_counter() - t0)   # E * world = NUM_ENVS
@@ -570,6 +620,9 @@ def main(argv=None) -> None:
     ap.add_argument("--fused-gru", action="store_true", help="the PPO update's GRU scan as the fused HIP operators")
     ap.add_argument("--fused-policy", action="store_true",
                     help="the rollout's policy step, sample and log-prob as one fused HIP launch")
+    ap.add_argument("--calc-eval", action="store_true",
+                    help="CALC_EVAL: after every update NUM_STEPS_EVAL sampled steps in a separate eval env (the same "
+                         "config, a synthetic day of another seed), logged as avg_reward_eval")
     ap.add_argument("--save", default=None, metavar="PATH", help="write a checkpoint here after the last update")
     ap.add_argument("--data", default=None, help="'lobster' to load world_config.dataPath (else synthetic)")
     a = ap.parse_args(argv)
@@ -583,12 +636,20 @@ def main(argv=None) -> None:
         c["FUSED_GRU"] = True
     if a.fused_policy:
         c["FUSED_POLICY"] = True
+    if a.calc_eval:
+        c["CALC_EVAL"] = True
     cfg = (load_config_from_file(a.env_config) if a.env_config.endswith((".json", ".yaml"))
            else builtin_config(a.env_config))
     env = MARLEnv(None, cfg, data=a.data, return_info=False, persistent_outputs=True)
     if not a.env_config.endswith((".json", ".yaml")):
         env.config_name = a.env_config   # what a checkpoint records instead of the config's dict
-    tr, sps = train(env, c, a.updates, log=lambda m: print(json.dumps(m)))
+    eval_env = None
+    if c["CALC_EVAL"]:
+        from ..data.synthetic import generate_day
+        w = cfg.world_config
+        day = generate_day(seed=1, snap_every=w.n_data_msg_per_step * w.start_resolution)
+        eval_env = MARLEnv(None, cfg, data=day, return_info=True, persistent_outputs=True)
+    tr, sps = train(env, c, a.updates, log=lambda m: print(json.dumps(m)), eval_env=eval_env)
     if a.save:
         tr.save_checkpoint(a.save)
     print(json.dumps({"env_steps_per_s_incl_learner": sps, "num_envs": c["NUM_ENVS"], "num_steps": c["NUM_STEPS"]}))
