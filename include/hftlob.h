@@ -598,6 +598,65 @@ int hftlob_policy_step_multi(int B, int D, int FC, int H, int K, const int* nvec
                              int32_t* action /*[B][K]*/, float* log_prob /*[B]*/, float* value /*[B]*/,
                              float* logits /*[B][S] or NULL*/, void* stream);
 
+/* Generalised advantage estimation of the learner (_calculate_gae, ippo_rnn_JAXMARL.py:668-690) as one
+ * launch, float32.  reward, value, adv, targets [T][n]; done bytes [T][n] (non-zero: the step ended the
+ * episode); last_val [n].  One lane owns one actor and walks t = T-1 .. 0 with gae = 0 and
+ * next_value = last_val at the start; with nd = 1.0f - done[t], every operation separately rounded:
+ *     delta      = (reward[t] + (gamma * next_value) * nd) - value[t]
+ *     gae        = delta + ((gamma_lambda * nd) * gae)
+ *     adv[t]     = gae        targets[t] = gae + value[t]        next_value = value[t]
+ * gamma and gamma_lambda are the caller's gamma and gamma * lambda (the product formed in double)
+ * rounded to float32; the result is hftlob/train/ippo.py calculate_gae bit for bit.
+ * HFTLOB_EINVAL: T or n < 1; HFTLOB_ENULL: a NULL pointer.  The call neither allocates nor synchronises,
+ * runs on the caller's stream and can be captured in a HIP graph. */
+int hftlob_gae(int T, int n, const float* reward, const float* value, const uint8_t* done,
+               const float* last_val /*[n]*/, float gamma, float gamma_lambda, float* adv, float* targets,
+               void* stream);
+
+/* The PPO objective of the learner (_loss_fn, ippo_rnn_JAXMARL.py:718-765, under MultiCategorical,
+ * :259-281) over N elements with its gradient, float32: hftlob/train/ippo.py ppo_loss_multi and what
+ * autograd makes of it.  K heads of widths nvec[k] (host, read at the call; they travel by value),
+ * S = sum nvec; logits [N][S], the heads side by side; actions int32 [N][K]; values, rb_value,
+ * rb_log_prob, adv, targets [N].  Every actions[i][k] must lie in [0, nvec[k]); this is a precondition the
+ * call does not check (a value outside it reads no memory out of bounds, but the result is undefined).
+ * Per element, with mean and the population std of adv over the N elements
+ * (accumulated in double):
+ *     A = (adv - mean) / (std + 1e-8)
+ *     lp_k = log_softmax(logits_k)   p_k = exp(lp_k)   H_k = -sum_j p_k[j] lp_k[j]
+ *     logp = sum_k lp_k[a_k]   ent = sum_k H_k   lr = logp - rb_log_prob   ratio = exp(lr)
+ *     a = ratio A              b = clamp(ratio, 1 - eps, 1 + eps) A
+ *     u = v - tgt              c = rb_v + clamp(v - rb_v, -eps, eps) - tgt
+ * out6 [6] (device) receives, as means over N,
+ *     value_loss = 0.5 mean(max(u^2, c^2))   actor_loss = -mean(min(a, b))   entropy = mean(ent)
+ *     approx_kl = mean((ratio - 1) - lr)     clip_frac = mean(|ratio - 1| > eps)
+ * in the order total = actor_loss + vf_coef value_loss - ent_coef entropy, value_loss, actor_loss,
+ * entropy, approx_kl, clip_frac.  d_logits [N][S] and d_values [N] receive the gradient of total for an
+ * upstream gradient of 1, in torch's conventions (minimum / maximum split a tie evenly, clamp passes
+ * the gradient on its inclusive bounds):
+ *     w = 1 if a < b, 0 if a > b, at a == b 1/2 + 1/2 [1 - eps <= ratio <= 1 + eps]
+ *     g_lp = -A w ratio / N
+ *     d_logits_k[j] = g_lp ([j == a_k] - p_k[j]) + (ent_coef / N) p_k[j] (lp_k[j] + H_k)
+ *     g_v = u if u^2 > c^2, c [-eps <= v - rb_v <= eps] if u^2 < c^2, half of each at equality
+ *     d_values = vf_coef g_v / N
+ * Both NULL: forward only, the same out6 bit for bit.  Three launches on the caller's stream (the
+ * moments of adv; the element pass, HFTLOB_PPO_LOSS_ROWS elements per workgroup, which writes the
+ * gradients and one row of partial sums per workgroup; the final sums), no floating-point atomic and a
+ * fixed order of every sum: the same inputs give the same bits.  workspace is
+ * HFTLOB_PPO_LOSS_WORKSPACE(N) doubles of the caller's, written before it is read.  The call neither
+ * allocates nor synchronises and can be captured in a HIP graph.
+ * HFTLOB_EINVAL: N < 1, K outside 1..4, an nvec[k] outside 1..16, exactly one of d_logits and d_values
+ * NULL; HFTLOB_ENULL: any other NULL pointer. */
+#define HFTLOB_PPO_LOSS_ROWS 64
+#define HFTLOB_PPO_LOSS_WS_HEAD 128   /* doubles: the moment partial sums */
+#define HFTLOB_PPO_LOSS_WS_ROW 5      /* doubles per workgroup of the element pass */
+#define HFTLOB_PPO_LOSS_WORKSPACE(N) \
+    (HFTLOB_PPO_LOSS_WS_HEAD + HFTLOB_PPO_LOSS_WS_ROW * (((long long)(N) + HFTLOB_PPO_LOSS_ROWS - 1) / HFTLOB_PPO_LOSS_ROWS))
+int hftlob_ppo_loss(int N, int K, const int* nvec /*[K], host*/, const float* logits /*[N][S]*/,
+                    const float* values, const int32_t* actions /*[N][K]*/, const float* rb_value,
+                    const float* rb_log_prob, const float* adv, const float* targets, double clip_eps,
+                    double vf_coef, double ent_coef, double* workspace, float* out6 /*[6], device*/,
+                    float* d_logits /*[N][S] or NULL*/, float* d_values /*[N] or NULL*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,7 @@ EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob
            "hftlob_env_rollout_actions", "hftlob_env_rollout_eval", "hftlob_eval_tally",
            "hftlob_env_lds_bytes", "hftlob_env_launch_info", "hftlob_env_baked_id", "hftlob_set_baked",
            "hftlob_sample_actions", "hftlob_split_keys", "hftlob_gru_scan_fwd", "hftlob_gru_scan_bwd",
-           "hftlob_policy_step", "hftlob_policy_step_multi")
+           "hftlob_policy_step", "hftlob_policy_step_multi", "hftlob_gae", "hftlob_ppo_loss")
 
 _lib = None
 
@@ -99,6 +99,11 @@ def lib() -> C.CDLL:
     L.hftlob_policy_step_multi.argtypes = [i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(PolicyWeights), vp, vp,
                                            vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.hftlob_policy_step_multi.restype = i32
+    L.hftlob_gae.argtypes = [i32, i32, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp]
+    L.hftlob_gae.restype = i32
+    L.hftlob_ppo_loss.argtypes = [i32, i32, C.POINTER(i32), vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double,
+                                  C.c_double, vp, vp, vp, vp, vp]
+    L.hftlob_ppo_loss.restype = i32
     if L.hftlob_version() != ABI_VERSION:
         raise RuntimeError(f"libhftlob ABI {L.hftlob_version()} != {ABI_VERSION}")
     _lib = L

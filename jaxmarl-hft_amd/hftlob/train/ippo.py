@@ -33,7 +33,8 @@ initialisation draw from torch's generator, not JAX's threefry, and the network
 runs through torch (rocBLAS GEMMs) rather than XLA.  With ``FUSED_POLICY`` the rollout's
 policy step is one HIP launch per agent type and step (``train.policy.policy_step``) and its
 samples are ``jax.random.categorical`` draws from a carried threefry key, so nothing inside the
-rollout reads torch's generator.
+rollout reads torch's generator.  With ``FUSED_LOSS`` the update's GAE is one HIP launch and the
+minibatch step's loss with its gradient three (``train.loss.gae``, ``train.loss.ppo_loss_fused``).
 """
 from __future__ import annotations
 
@@ -48,6 +49,7 @@ import torch.nn.functional as F
 
 from ..env import MARLEnv, split_keys
 from .gru import SUPPORTED_HIDDEN, gru_scan, gru_scan_supported
+from .loss import gae as gae_fused, ppo_loss_fused, ppo_loss_supported
 from .policy import MAX_ACTIONS, MAX_HEADS, MAX_OBS_DIM, SAMPLE, policy_step_multi_supported, policy_step_net
 
 
@@ -63,7 +65,7 @@ def default_config(**kw) -> Dict:
          "TOTAL_TIMESTEPS": 5e8, "UPDATE_EPOCHS": 4, "NUM_MINIBATCHES": 4, "GAMMA": [0.999999999, 0.999],
          "GAE_LAMBDA": [0.85, 0.9], "CLIP_EPS": 0.2, "ENT_COEF": [0.01, 0.01], "VF_COEF": [0.5, 0.5],
          "MAX_GRAD_NORM": [0.5, 0.5], "ANNEAL_LR": [True, True], "NUM_AGENTS_PER_TYPE": [1, 1], "SEED": 2,
-         "CUDA_GRAPHS": True, "FUSED_GRU": False, "FUSED_POLICY": False,
+         "CUDA_GRAPHS": True, "FUSED_GRU": False, "FUSED_POLICY": False, "FUSED_LOSS": False,
          "CALC_EVAL": False, "NUM_STEPS_EVAL": None}   # NUM_STEPS_EVAL None: NUM_STEPS
     c.update(kw)
     return c
@@ -278,6 +280,16 @@ class IPPOTrainer:
                                      f"an observation size <= {MAX_OBS_DIM} and <= {MAX_ACTIONS} actions (in each of "
                                      f"<= {MAX_HEADS} heads), got {c['GRU_HIDDEN_DIM']}, {c['FC_DIM_SIZE']}, {D} and "
                                      f"{n.heads} (agent type {i})")
+        # FUSED_LOSS: the update's GAE as one HIP launch and the minibatch step's loss with its gradient as
+        # three (train.loss.gae, train.loss.ppo_loss_fused; GPU only, and there is no other path behind the switch)
+        self.fused_loss = bool(c.get("FUSED_LOSS", False))
+        if self.fused_loss:
+            if self.device.type != "cuda":
+                raise ValueError(f"FUSED_LOSS needs a GPU device, got {self.device}")
+            for i, n in enumerate(self.nets):
+                if not ppo_loss_supported(n.heads):
+                    raise ValueError(f"FUSED_LOSS needs <= {MAX_ACTIONS} actions (in each of <= {MAX_HEADS} heads), "
+                                     f"got {n.heads} (agent type {i})")
         # CALC_EVAL (:461-482, 876-975): after every update NUM_STEPS_EVAL sampled steps of the current nets
         # in a separate eval env, through the fused policy step and the tally launch (evaluate_policy)
         self.calc_eval = bool(c.get("CALC_EVAL", False))
@@ -429,9 +441,10 @@ class IPPOTrainer:
         c, net, opt, b, st = self.c, self.nets[i], self.opts[i], self.buf[i], self._st[i]
         idx = st["idx"]
         logits, values = net(st["h0"][idx], b.obs[:, idx], b.done[:, idx])
-        out = ppo_loss_multi(logits, values, b.action[:, idx].view(self.T, -1, len(net.heads)), b.value[:, idx],
-                             b.log_prob[:, idx], st["adv"][:, idx], st["tgt"][:, idx], c["CLIP_EPS"], c["VF_COEF"][i],
-                             c["ENT_COEF"][i], net.heads)
+        loss_fn = ppo_loss_fused if self.fused_loss else ppo_loss_multi
+        out = loss_fn(logits, values, b.action[:, idx].view(self.T, -1, len(net.heads)), b.value[:, idx],
+                      b.log_prob[:, idx], st["adv"][:, idx], st["tgt"][:, idx], c["CLIP_EPS"], c["VF_COEF"][i],
+                      c["ENT_COEF"][i], net.heads)
         out[0].backward()
         if self.dist is not None and self.dist.get_world_size() > 1:
             _average_grads(list(net.parameters()), self.dist)
@@ -474,8 +487,8 @@ class IPPOTrainer:
             st = self._static(i, n, mb)
             with torch.no_grad():
                 _, _, last_val = net.step(self.h[i], self.last_obs[i], self.last_done[i])
-                adv, targets = calculate_gae(b.reward, b.value, b.global_done, last_val, c["GAMMA"][i],
-                                             c["GAE_LAMBDA"][i])
+                gae_fn = gae_fused if self.fused_loss else calculate_gae
+                adv, targets = gae_fn(b.reward, b.value, b.global_done, last_val, c["GAMMA"][i], c["GAE_LAMBDA"][i])
                 st["h0"].copy_(h0[i]); st["adv"].copy_(adv); st["tgt"].copy_(targets)
             stats = torch.zeros(6, device=self.device)
             for _ in range(c["UPDATE_EPOCHS"]):
@@ -620,6 +633,8 @@ def main(argv=None) -> None:
     ap.add_argument("--fused-gru", action="store_true", help="the PPO update's GRU scan as the fused HIP operators")
     ap.add_argument("--fused-policy", action="store_true",
                     help="the rollout's policy step, sample and log-prob as one fused HIP launch")
+    ap.add_argument("--fused-loss", action="store_true",
+                    help="the update's GAE and PPO loss (with its gradient) as fused HIP launches")
     ap.add_argument("--calc-eval", action="store_true",
                     help="CALC_EVAL: after every update NUM_STEPS_EVAL sampled steps in a separate eval env (the same "
                          "config, a synthetic day of another seed), logged as avg_reward_eval")
@@ -636,6 +651,8 @@ def main(argv=None) -> None:
         c["FUSED_GRU"] = True
     if a.fused_policy:
         c["FUSED_POLICY"] = True
+    if a.fused_loss:
+        c["FUSED_LOSS"] = True
     if a.calc_eval:
         c["CALC_EVAL"] = True
     cfg = (load_config_from_file(a.env_config) if a.env_config.endswith((".json", ".yaml"))

@@ -1,10 +1,12 @@
 """Time the IPPO learner's phases on the GPU (rollout vs PPO epochs) at the metric config.
 
-    python tools/train_timing.py [--graph] [--fused-gru] [--fused-policy]
+    python tools/train_timing.py [--graph] [--fused-gru] [--fused-policy] [--fused-loss]
 
 --graph: CUDA_GRAPHS (the rollout and each minibatch step replayed as HIP graphs);
 --fused-gru: FUSED_GRU (the minibatch step's GRU scan through hftlob_gru_scan_fwd / _bwd);
---fused-policy: FUSED_POLICY (the rollout's policy step, sample and log-prob through hftlob_policy_step)."""
+--fused-policy: FUSED_POLICY (the rollout's policy step, sample and log-prob through hftlob_policy_step);
+--fused-loss: FUSED_LOSS (the update's GAE through hftlob_gae, the minibatch step's loss and its gradient through
+hftlob_ppo_loss)."""
 import os
 import sys
 import time
@@ -27,7 +29,8 @@ def main():
     env = MARLEnv(None, cfg, data=day, return_info=False, persistent_outputs=True)
     graph = "--graph" in sys.argv
     c = I.default_config(NUM_ENVS=4096, NUM_STEPS=64, TOTAL_TIMESTEPS=4096 * 64 * 50, CUDA_GRAPHS=graph,
-                         FUSED_GRU="--fused-gru" in sys.argv, FUSED_POLICY="--fused-policy" in sys.argv)
+                         FUSED_GRU="--fused-gru" in sys.argv, FUSED_POLICY="--fused-policy" in sys.argv,
+                         FUSED_LOSS="--fused-loss" in sys.argv)
     tr = I.IPPOTrainer(env, c)
     tr.update()
     torch.cuda.synchronize()
