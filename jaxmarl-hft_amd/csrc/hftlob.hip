@@ -425,12 +425,19 @@ struct Side {
     // from the last recording lane before them when the chunk ends
     i32 rp, rq;
     lmask rm;
+#ifdef HFTLOB_STAMPS_CHUNK  // diagnostic build only: the step's rescans and best-quote records of this side
+    u32 n_resc, n_rec;
+#endif
 };
 // a message (its lane k of the chunk) set or recomputed the side's best quote: record it
-template <int S> DEV void side_rec(Side<S>& s, u32 k) {
+// LZ (the lazy-volume mode, see rescan): the price only
+template <bool LZ = false, int S> DEV void side_rec(Side<S>& s, u32 k) {
     s.rp = wlane(s.rp, s.best_p, (int)k);
-    s.rq = wlane(s.rq, s.best_q, (int)k);
+    if (!LZ) s.rq = wlane(s.rq, s.best_q, (int)k);
     asm volatile("s_bitset1_b64 %0, %1" : "+s"(s.rm) : "s"(k));
+#ifdef HFTLOB_STAMPS_CHUNK
+    ++s.n_rec;
+#endif
 }
 
 // slot e of a lane-strided register column <- v (lane e & 63 of register e >> 6): one
@@ -457,7 +464,9 @@ template <int S> DEV void col_set(i32 (&c)[S], int e, i32 v) {
 // (bit 0 is left unused: a branch on a bit-0 test compiles to s_bitcmp1 + a 64-bit lane mask
 // + s_and_b64 exec + s_cbranch_vccnz, on any other bit to s_bitcmp1 + s_cbranch_scc)
 enum : u32 { F_STALE_A = 2, F_STALE_B = 4, F_CLEAN_A = 8, F_CLEAN_B = 16, F_NEG1_A = 32, F_NEG1_B = 64,
-             F_PM1_A = 256, F_PM1_B = 512, F_STALE_ANY = 0x40000000u, F_SLOW = 0x80000000u };
+             F_PM1_A = 256, F_PM1_B = 512, F_LAZY = 0x20000000u, F_STALE_ANY = 0x40000000u, F_SLOW = 0x80000000u };
+// F_LAZY is never in Book::fl: a lazy-volume step (rescan's LZ) sets it in the flags it hands to the
+// wave's next resident step, whose carried best_q words are then not valid (env_step_dev)
 constexpr u32 STALE_ANY = F_STALE_ANY;  // set with either side's STALE bit: one bit test after each message
 template <bool ASKS> struct SideBits {
     static constexpr u32 STALE = ASKS ? F_STALE_A : F_STALE_B;
@@ -602,16 +611,43 @@ DEV void best_ask_pq(const i32 (&p)[S], const i32 (&q)[S], const Valid<S>& V, i3
     bp = pa;
     bq = wave_sum(v);
 }
+// the price halves of best_bid_pq / best_ask_pq: the register price column alone, no LDS access
+template <int S> DEV i32 best_bid_p(const i32 (&p)[S], const Valid<S>& V) {
+    i32 m = INT_MIN;
+#pragma unroll
+    for (int r = 0; r < S; ++r) m = imax_(m, V.v[r] ? p[r] : INT_MIN);
+    return wave_max(m);
+}
+template <int S> DEV i32 best_ask_p(const i32 (&p)[S], const Valid<S>& V, i32 maxint, i32& xp) {
+    i32 m = INT_MAX;
+#pragma unroll
+    for (int r = 0; r < S; ++r) m = imin_(m, V.v[r] ? (p[r] == -1 ? maxint : p[r]) : INT_MAX);
+    const i32 mn = wave_min(m);
+    xp = mn;
+    return mn == maxint ? -1 : mn;
+}
 // recompute a side's cached best quote (clears its STALE bit); REC: inside message k's
-// processing, which then records the quote
-template <bool ASKS, bool REC, int S>
+// processing, which then records the quote.
+// LZ, the lazy-volume mode of a quiet resident step whose best-quote volumes nobody reads
+// (env_step_dev's LAZY): best_q is neither kept nor read anywhere, the rescan is the price half
+// alone, and a level's exhaustion is found from the price column where a row is cleared
+// (note_reduce) instead of from best_q <= 0
+template <bool ASKS, bool REC, bool LZ = false, int S>
 DEV void rescan(Side<S>& s, u32& fl, int R, const Valid<S>& V, i32 maxint, u32 k) {
-    i32 q[S];
-    ldcol(s.t, R, FQ, q);
-    if (ASKS) best_ask_pq(s.pc, q, V, maxint, s.best_p, s.best_q, &s.xp);
-    else best_bid_pq(s.pc, q, V, s.best_p, s.best_q);
+    if (LZ) {
+        if (ASKS) s.best_p = best_ask_p(s.pc, V, maxint, s.xp);
+        else s.best_p = best_bid_p(s.pc, V);
+    } else {
+        i32 q[S];
+        ldcol(s.t, R, FQ, q);
+        if (ASKS) best_ask_pq(s.pc, q, V, maxint, s.best_p, s.best_q, &s.xp);
+        else best_bid_pq(s.pc, q, V, s.best_p, s.best_q);
+    }
     fl &= ~SideBits<ASKS>::STALE;
-    if (REC) side_rec(s, k);
+    if (REC) side_rec<LZ>(s, k);
+#ifdef HFTLOB_STAMPS_CHUNK
+    ++s.n_resc;
+#endif
 }
 
 // _get_top_bid_order_idx / _get_top_ask_order_idx — :241-268 (exact formulas);
@@ -787,7 +823,9 @@ template <int S> DEV void top_eq(Side<S>& s, int e, i32 t, i32 tns, i32 maxint) 
 // the other side before it gets here)
 #define XP_SET(s, v) ((s).xp = (v))  // (asks: a new best price below maxint)
 // NN: np >= 0 is known (the common adds: decode_msgs marks negative prices RARE)
-template <bool BID, int S, bool STALE_OK = true, bool NN = false>
+// LZ (rescan): an order joining the best level changes neither the price nor its record, only the
+// top-of-book cache
+template <bool BID, int S, bool STALE_OK = true, bool NN = false, bool LZ = false>
 DEV void note_add(Side<S>& s, u32& fl, int e, i32 np, i32 nq, i32 t, i32 tns, i32 maxint, u32 k) {
     // an all -1 row (slot e) now holds (np, nq > 0, time t / tns).  Branches ordered for the
     // common case, an order behind the best (one compare each); per side the cases are those of
@@ -799,14 +837,14 @@ DEV void note_add(Side<S>& s, u32& fl, int e, i32 np, i32 nq, i32 t, i32 tns, i3
         if (np < bp) {
             if (!NN && bp == -1) fl |= MARK;  // np < -1 on an empty side
         } else if (np > bp) {
-            s.best_p = np; s.best_q = nq;   // (an empty side: np > -1)
-            side_rec(s, k);
+            s.best_p = np;                  // (an empty side: np > -1)
+            if (!LZ) s.best_q = nq;
+            side_rec<LZ>(s, k);
             top_new(s, e, np, t, tns, maxint);
         } else if (!NN && bp == -1) {
             fl |= MARK;                       // np == -1 on an empty side
         } else {
-            s.best_q = wadd(s.best_q, nq);
-            side_rec(s, k);
+            if (!LZ) { s.best_q = wadd(s.best_q, nq); side_rec(s, k); }
             top_eq(s, e, t, tns, maxint);
         }
     } else if (NN && !STALE_OK) {
@@ -817,38 +855,52 @@ DEV void note_add(Side<S>& s, u32& fl, int e, i32 np, i32 nq, i32 t, i32 tns, i3
         const i32 xp = s.xp;
         if (np > xp) {
         } else if (np < xp) {
-            s.best_p = np; s.best_q = nq; XP_SET(s, np); side_rec(s, k); top_new(s, e, np, t, tns, maxint);
+            s.best_p = np; if (!LZ) s.best_q = nq; XP_SET(s, np); side_rec<LZ>(s, k); top_new(s, e, np, t, tns, maxint);
         } else if (np == maxint) {
             fl |= MARK;
         } else {
-            s.best_q = wadd(s.best_q, nq);
-            side_rec(s, k);
+            if (!LZ) { s.best_q = wadd(s.best_q, nq); side_rec(s, k); }
             top_eq(s, e, t, tns, maxint);
         }
     } else {
         if (np > bp) {
             if (bp == -1) {                 // empty side
                 if (np == maxint) fl |= MARK;
-                else { s.best_p = np; s.best_q = nq; XP_SET(s, np); side_rec(s, k); top_new(s, e, np, t, tns, maxint); }
+                else { s.best_p = np; if (!LZ) s.best_q = nq; XP_SET(s, np); side_rec<LZ>(s, k); top_new(s, e, np, t, tns, maxint); }
             }
         } else if (np < bp) {
-            if (NN || np != -1) { s.best_p = np; s.best_q = nq; XP_SET(s, np); side_rec(s, k); top_new(s, e, np, t, tns, maxint); }
+            if (NN || np != -1) { s.best_p = np; if (!LZ) s.best_q = nq; XP_SET(s, np); side_rec<LZ>(s, k); top_new(s, e, np, t, tns, maxint); }
         } else if (!NN && np == -1) {
             fl |= MARK;
         } else if (np != maxint) {
-            s.best_q = wadd(s.best_q, nq);
-            side_rec(s, k);
+            if (!LZ) { s.best_q = wadd(s.best_q, nq); side_rec(s, k); }
             top_eq(s, e, t, tns, maxint);
         }
     }
 }
-// a row at price op lost dq of its quantity (possibly all of it)
-template <bool ASKS, int S> DEV void note_reduce(Side<S>& s, u32& fl, i32 op, i32 dq, u32 k) {
+// a row at price op lost dq of its quantity (possibly all of it: `cleared`, the row is gone)
+// LZ (rescan): no best_q to tell that the best level is exhausted.  On a FAST book (!G) a row is
+// cleared exactly when its quantity falls to <= 0 and every remaining row at a price holds q > 0, so
+// after a row at best_p was cleared the level is exhausted iff no slot of the price column still
+// holds best_p (best_p != -1 here, and the column's slots past the side's rows hold -1); a
+// reduction that leaves the row in place never exhausts it.  The lane masks of the test live only
+// inside this path.  The general handlers (G) mark the side stale instead: the rescan decides.
+template <bool ASKS, bool LZ = false, bool G = false, int S>
+DEV void note_reduce(Side<S>& s, u32& fl, i32 op, i32 dq, u32 k, bool cleared) {
     constexpr u32 STALE = SideBits<ASKS>::STALE, MARK = SideBits<ASKS>::MARK;
     if (fl & STALE) return;
     if (op == s.best_p) {
         if (op == -1) {
             fl |= MARK;
+        } else if (LZ) {
+            if (G) {
+                fl |= MARK;
+            } else if (cleared) {
+                lmask at = 0;
+#pragma unroll
+                for (int r = 0; r < S; ++r) at |= bal(s.pc[r] == op);
+                if (at == 0ull) fl |= MARK;  // level exhausted: rescan
+            }
         } else {
             s.best_q = wsub(s.best_q, dq);
             side_rec(s, k);
@@ -891,7 +943,7 @@ template <int S> DEV bool no_slot(const lmask (&m)[S]) {
 // match_order — JaxOrderBookArrays.py:172-220
 // (qt, pt, ot, tt): the top slot's quantity, price, order id, trader id;
 // tr4: the trade log's OID column
-template <bool G, bool ASKS, int S>
+template <bool G, bool ASKS, bool LZ = false, int S>
 DEV i32 match_order(Book<S>& B, Side<S>& s, int top, i32 qtm, const Msg& m, i32 qt, i32 pt, i32 ot, i32 tt) {
     const int R = B.c.nO;
     const i32 newq = imax_(0, wsub(qt, qtm));
@@ -913,7 +965,7 @@ DEV i32 match_order(Book<S>& B, Side<S>& s, int top, i32 qtm, const Msg& m, i32 
     if (!G || (B.fl & SideBits<ASKS>::CLEAN)) {
         if (newq <= 0) side_clr(s, R, top);
         else stu(s.t, s.scr, R, FQ, top, newq);
-        note_reduce<ASKS>(s, B.fl, pt, wsub(qt, newq), m.k);
+        note_reduce<ASKS, LZ, G>(s, B.fl, pt, wsub(qt, newq), m.k, newq <= 0);
     } else {
         stu(s.t, s.scr, R, FQ, top, newq);
         rzn<ASKS>(s, B.fl, R, B.vs);
@@ -926,7 +978,7 @@ DEV i32 match_order(Book<S>& B, Side<S>& s, int top, i32 qtm, const Msg& m, i32 
 // a crossing best pays for the 3-reduction top-of-book.
 // a crossing trip loads every column it needs at once (one LDS round trip)
 // POS: qtm > 0 is known (the common FAST adds, decode_msgs)
-template <bool BID, bool G, int S, bool POS = false>
+template <bool BID, bool G, int S, bool POS = false, bool LZ = false>
 DEV i32 match_against(Book<S>& B, Side<S>& s, i32 qtm, i32 price, const Msg& m) {
     const int R = B.c.nO;
     // the common case first, as straight-line scalar code: nothing to match, or a best that
@@ -940,7 +992,7 @@ DEV i32 match_against(Book<S>& B, Side<S>& s, i32 qtm, i32 price, const Msg& m) 
         if (__builtin_expect(BID ? mp0 < price : mp0 > price, 1)) return qtm;
     }
     while (qtm > 0) {
-        if (B.fl & SideBits<!BID>::STALE) rescan<!BID, true>(s, B.fl, R, B.vs, B.c.maxint, m.k);
+        if (B.fl & SideBits<!BID>::STALE) rescan<!BID, true, LZ>(s, B.fl, R, B.vs, B.c.maxint, m.k);
         // the side's best; an empty ask side (-1) counts as maxint (_get_top_ask_order_idx).
         // BID: `s` is the bid side (an incoming sell crosses when best bid >= price)
         i32 mp = s.best_p;
@@ -977,14 +1029,14 @@ DEV i32 match_against(Book<S>& B, Side<S>& s, i32 qtm, i32 price, const Msg& m) 
         if (fresh(tp) == -1) break;  // (two branches, not a 64-bit lane-mask OR)
         asm volatile("");
         if (BID ? tp < price : tp > price) break;
-        qtm = match_order<G, !BID>(B, s, top, qtm, m, qt, tp, ot, tt);
+        qtm = match_order<G, !BID, LZ>(B, s, top, qtm, m, qt, tp, ot, tt);
     }
     return qtm;
 }
 
 // add_order — :62-83 (first slot holding ANY -1 field; none -> last slot)
 // free: the side's p == -1 slots (from the caller)
-template <bool BID, bool G, int S>
+template <bool BID, bool G, bool LZ = false, int S>
 DEV void add_order(Book<S>& B, Side<S>& s, const Msg& m, i32 qty, const lmask (&free)[S]) {
     const int R = B.c.nO;
     constexpr u32 CLEAN = SideBits<!BID>::CLEAN, NEG1 = SideBits<!BID>::NEG1, MARK = SideBits<!BID>::MARK,
@@ -996,7 +1048,7 @@ DEV void add_order(Book<S>& B, Side<S>& s, const Msg& m, i32 qty, const lmask (&
         if (nq > 0) {
             side_put(s, R, e, m.price, nq, m.oid, m.tid, m.t, m.tns);
             if (m.h & (H_NEG1 | H_PM1)) B.fl = B.fl | (m.h & H_NEG1 ? NEG1 : 0u) | (m.h & H_PM1 ? PM1 : 0u) | F_SLOW;
-            if (was_empty) note_add<BID>(s, B.fl, e, m.price, nq, m.t, m.tns, B.c.maxint, m.k);
+            if (was_empty) note_add<BID, S, true, false, LZ>(s, B.fl, e, m.price, nq, m.t, m.tns, B.c.maxint, m.k);
             else { B.fl |= MARK; s.top = -1; }
         } else if (!was_empty) {  // the new row is removed at once: net effect clears row e
             side_clr(s, R, e);
@@ -1032,7 +1084,7 @@ DEV void add_order(Book<S>& B, Side<S>& s, const Msg& m, i32 qty, const lmask (&
         side_put(s, R, e, m.price, nq, m.oid, m.tid, m.t, m.tns);
         if (m.h & H_NEG1) B.fl |= NEG1;
         if (m.h & H_PM1) B.fl |= PM1;
-        if (was_empty) note_add<BID>(s, B.fl, e, m.price, nq, m.t, m.tns, B.c.maxint, m.k);
+        if (was_empty) note_add<BID, S, true, false, LZ>(s, B.fl, e, m.price, nq, m.t, m.tns, B.c.maxint, m.k);
         else { B.fl |= MARK; s.top = -1; }
     } else if (!was_empty) {  // the new row is removed at once: net effect clears row e
         side_clr(s, R, e);
@@ -1070,7 +1122,7 @@ template <bool BID, int S> DEV void evict_if_full(Book<S>& B, Side<S>& s, lmask 
 // first free slot (add_order's "first row holding any -1").  Flag changes are rare (orders with
 // -1 fields), so they stay behind a branch.
 // POS: qty > 0 is known (the common add that does not cross)
-template <bool BID, bool RARE, int S, bool POS = false>
+template <bool BID, bool RARE, int S, bool POS = false, bool LZ = false>
 DEV void add_free(Book<S>& B, Side<S>& s, const Msg& m, i32 qty, const lmask (&free)[S]) {
     const int R = B.c.nO;
     if (!POS && qty <= 0) return;  // imax(0, qty) == 0: the new row is removed at once and the slot was empty
@@ -1097,79 +1149,79 @@ DEV void add_free(Book<S>& B, Side<S>& s, const Msg& m, i32 qty, const lmask (&f
         constexpr u32 NEG1 = SideBits<!BID>::NEG1, PM1 = SideBits<!BID>::PM1;
         B.fl = B.fl | (m.h & H_NEG1 ? NEG1 : 0u) | (m.h & H_PM1 ? PM1 : 0u) | F_SLOW;
     }
-    note_add<BID, S, false, !RARE>(s, B.fl, (int)e, m.price, qty, m.t, m.tns, B.c.maxint, m.k);
+    note_add<BID, S, false, !RARE, LZ>(s, B.fl, (int)e, m.price, qty, m.t, m.tns, B.c.maxint, m.k);
 }
 // the common non-crossing add into a side with a free slot (false: the side is full).  Two register
 // sets: the first set's free slot is tested first, alone (the usual case: one branch, and the row
 // write follows it without a jump), then the second's
-template <bool BID, int S> DEV bool add_common(Book<S>& B, Side<S>& s, const Msg& m, const lmask (&free)[S]) {
+template <bool BID, bool LZ = false, int S> DEV bool add_common(Book<S>& B, Side<S>& s, const Msg& m, const lmask (&free)[S]) {
 #ifndef HFTLOB_OLD_ADD_TEST  // (A/B builds only)
     if (S == 2) {
         if (__builtin_expect(free[0] != 0ull, 1)) {
-            add_free<BID, false, S, true>(B, s, m, m.qty, free);
+            add_free<BID, false, S, true, LZ>(B, s, m, m.qty, free);
             return true;
         }
         if (free[S - 1] == 0ull) return false;
-        add_free<BID, false, S, true>(B, s, m, m.qty, free);
+        add_free<BID, false, S, true, LZ>(B, s, m, m.qty, free);
         return true;
     }
 #endif
     if (no_slot(free)) return false;
-    add_free<BID, false, S, true>(B, s, m, m.qty, free);
+    add_free<BID, false, S, true, LZ>(B, s, m, m.qty, free);
     return true;
 }
 // bid_lim — :357-420 (the eviction persists when the add is discarded)
 // RARE = false: the message has none of the H_RARE flags (MKT, discard, -1 fields), so their
 // tests are compiled out of the common FAST add
-template <bool G, bool RARE, int S> DEV void bid_lim(Book<S>& B, Msg m) {
+template <bool G, bool RARE, bool LZ = false, int S> DEV void bid_lim(Book<S>& B, Msg m) {
     if (!RARE) __builtin_assume(m.qty > 0);  // (decode_msgs: an add of no quantity is RARE)
     constexpr bool POS = !RARE && !G;
     if (POS) {  // the common add: it does not cross (an empty ask side stands for maxint), so all of it goes in
         if (__builtin_expect(B.a.xp > m.price, 1)) {  // (xp: the best ask, an empty side maxint)
             lmask free[S];
             free_slots(B, B.b, free);
-            if (add_common<true>(B, B.b, m, free)) return;
+            if (add_common<true, LZ>(B, B.b, m, free)) return;
             if (B.c.check_fill) evict_if_full<true>(B, B.b, free);
-            add_order<true, G>(B, B.b, m, m.qty, free);
+            add_order<true, G, LZ>(B, B.b, m, m.qty, free);
             return;
         }
     }
-    const i32 rem = match_against<false, G, S, POS>(B, B.a, m.qty, m.price, m);
+    const i32 rem = match_against<false, G, S, POS, LZ>(B, B.a, m.qty, m.price, m);
     if (RARE && __builtin_expect((m.h & H_MKT) != 0, 0)) m.price = B.c.maxint;  // MKT: set after matching (sic)
     lmask free[S];
     free_slots(B, B.b, free);
     if (!no_slot(free)) {
         // FAST: a discarded add is an add of nothing (add_free returns at once for qty <= 0)
-        if (!G) add_free<true, RARE>(B, B.b, m, (RARE && (m.h & H_DISCARD)) ? 0 : rem, free);
-        else if (!(m.h & H_DISCARD)) add_order<true, G>(B, B.b, m, rem, free);
+        if (!G) add_free<true, RARE, S, false, LZ>(B, B.b, m, (RARE && (m.h & H_DISCARD)) ? 0 : rem, free);
+        else if (!(m.h & H_DISCARD)) add_order<true, G, LZ>(B, B.b, m, rem, free);
         return;
     }
     if (B.c.check_fill) evict_if_full<true>(B, B.b, free);
-    if (!(m.h & H_DISCARD)) add_order<true, G>(B, B.b, m, rem, free);
+    if (!(m.h & H_DISCARD)) add_order<true, G, LZ>(B, B.b, m, rem, free);
 }
 // ask_lim — :446-508
-template <bool G, bool RARE, int S> DEV void ask_lim(Book<S>& B, Msg m) {
+template <bool G, bool RARE, bool LZ = false, int S> DEV void ask_lim(Book<S>& B, Msg m) {
     if (!RARE) __builtin_assume(m.qty > 0);  // (decode_msgs: an add of no quantity is RARE)
     if (RARE && __builtin_expect((m.h & H_MKT) != 0, 0)) m.price = 0;
     constexpr bool POS = !RARE && !G;
     if (POS && __builtin_expect(B.b.best_p < m.price, 1)) {  // the common add: it does not cross
         lmask free[S];
         free_slots(B, B.a, free);
-        if (add_common<false>(B, B.a, m, free)) return;
+        if (add_common<false, LZ>(B, B.a, m, free)) return;
         if (B.c.check_fill) evict_if_full<false>(B, B.a, free);
-        add_order<false, G>(B, B.a, m, m.qty, free);
+        add_order<false, G, LZ>(B, B.a, m, m.qty, free);
         return;
     }
-    const i32 rem = match_against<true, G, S, POS>(B, B.b, m.qty, m.price, m);
+    const i32 rem = match_against<true, G, S, POS, LZ>(B, B.b, m.qty, m.price, m);
     lmask free[S];
     free_slots(B, B.a, free);
     if (!no_slot(free)) {
-        if (!G) add_free<false, RARE>(B, B.a, m, (RARE && (m.h & H_DISCARD)) ? 0 : rem, free);
-        else if (!(m.h & H_DISCARD)) add_order<false, G>(B, B.a, m, rem, free);
+        if (!G) add_free<false, RARE, S, false, LZ>(B, B.a, m, (RARE && (m.h & H_DISCARD)) ? 0 : rem, free);
+        else if (!(m.h & H_DISCARD)) add_order<false, G, LZ>(B, B.a, m, rem, free);
         return;
     }
     if (B.c.check_fill) evict_if_full<false>(B, B.a, free);
-    if (!(m.h & H_DISCARD)) add_order<false, G>(B, B.a, m, rem, free);
+    if (!(m.h & H_DISCARD)) add_order<false, G, LZ>(B, B.a, m, rem, free);
 }
 // get_random_id_match / get_random_large_id_match — :141-164 (cancel_mode 2/3).
 // key = split(key)[0]; chosen = jax.random.choice(key, ids, p=|sign(ids)|),
@@ -1211,7 +1263,7 @@ DEV int random_id_match(const Book<S>& B, Key& k, const i32 (&o)[S], const lmask
     return first_slot(f, -1);
 }
 // cancel_order + get_init_id_match — :93-139 (+ :141-164 when RC)
-template <bool G, bool ASKS, bool RC, int S> DEV void cancel(Book<S>& B, Side<S>& s, const Msg& m) {
+template <bool G, bool ASKS, bool RC, bool LZ = false, int S> DEV void cancel(Book<S>& B, Side<S>& s, const Msg& m) {
     // On clean sides (the !G variant) a zero-quantity cancel changes nothing: whichever row it
     // picks keeps q (or, empty, stays all -1) and the best quote is unchanged.  The agents'
     // unused cancel rows (getCancelMsgs' zero rows) are such messages.
@@ -1306,7 +1358,7 @@ template <bool G, bool ASKS, bool RC, int S> DEV void cancel(Book<S>& B, Side<S>
     if (!G || (B.fl & SideBits<ASKS>::CLEAN)) {
         if (nq <= 0) side_clr(s, R, idx);
         else stu(s.t, s.scr, R, FQ, idx, nq);
-        note_reduce<ASKS>(s, B.fl, op, wsub(oq, nq > 0 ? nq : 0), m.k);
+        note_reduce<ASKS, LZ, G>(s, B.fl, op, wsub(oq, nq > 0 ? nq : 0), m.k, nq <= 0);
     } else {
         stu(s.t, s.scr, R, FQ, idx, nq);
         rzn<ASKS>(s, B.fl, R, B.vs);
@@ -1345,29 +1397,29 @@ DEV void decode_msgs(const LobCfg& c, int4& x, const int4& y) {
 }
 // sdv: the chunk's side register (decode_msgs), read at lane k only where a handler needs the
 // side: a common (not RARE) bid has side 1 and a common ask -1, and only matches record it
-template <bool G, bool RC, int S>
+template <bool G, bool RC, bool LZ = false, int S>
 DEV void process_msg_(Book<S>& B, u32 k, i32 h, i32 sdv, i32 d2, i32 d3, i32 d4, i32 d5, i32 d6, i32 d7) {
     Msg m;
     m.h = h; m.side = 0; m.price = d3; m.qty = d2; m.oid = d4; m.tid = d5; m.t = d6; m.tns = d7;
     m.k = k;
     const i32 kind = h & H_KIND;
-    if (kind == H_CNL_ASK) cancel<G, true, RC>(B, B.a, m);
-    else if (kind == H_CNL_BID) cancel<G, false, RC>(B, B.b, m);
+    if (kind == H_CNL_ASK) cancel<G, true, RC, LZ>(B, B.a, m);
+    else if (kind == H_CNL_BID) cancel<G, false, RC, LZ>(B, B.b, m);
     else if (kind == H_BID) {
         if (!G && !(h & H_RARE)) {
             m.side = 1;
-            bid_lim<G, false>(B, m);
+            bid_lim<G, false, LZ>(B, m);
         } else {
             m.side = rdl(sdv, k);
-            bid_lim<G, true>(B, m);
+            bid_lim<G, true, LZ>(B, m);
         }
     } else if (kind == H_ASK) {
         if (!G && !(h & H_RARE)) {
             m.side = -1;
-            ask_lim<G, false>(B, m);
+            ask_lim<G, false, LZ>(B, m);
         } else {
             m.side = rdl(sdv, k);
-            ask_lim<G, true>(B, m);
+            ask_lim<G, true, LZ>(B, m);
         }
     }
 }
@@ -1381,10 +1433,10 @@ DEV i32 ffill(i32 v, i32 carry) {
     return src < 0 ? carry : got;
 }
 // REC: after message k (which records the recomputed quotes), not at a chunk's start
-template <bool REC = true, int S> DEV void refresh_best(Book<S>& B, u32 k = 0) {
+template <bool REC = true, bool LZ = false, int S> DEV void refresh_best(Book<S>& B, u32 k = 0) {
     if (B.fl & STALE_ANY) {
-        if (B.fl & F_STALE_A) rescan<true, REC>(B.a, B.fl, B.c.nO, B.vs, B.c.maxint, k);
-        if (B.fl & F_STALE_B) rescan<false, REC>(B.b, B.fl, B.c.nO, B.vs, B.c.maxint, k);
+        if (B.fl & F_STALE_A) rescan<true, REC, LZ>(B.a, B.fl, B.c.nO, B.vs, B.c.maxint, k);
+        if (B.fl & F_STALE_B) rescan<false, REC, LZ>(B.b, B.fl, B.c.nO, B.vs, B.c.maxint, k);
         B.fl &= ~STALE_ANY;
     }
 }
@@ -1507,7 +1559,8 @@ template <bool RC, int S> DEV lmask chunk_noops(Book<S>& B, const int4& x, const
 #define CHUNK_PARAMS
 #define CHUNK_ARGS
 #endif
-template <bool RC, int S>
+// LZ (rescan): the price record only; rqa / rqb come back 0
+template <bool RC, bool LZ = false, int S>
 DEV void run_chunk(Book<S>& B, const int4& x, const int4& y, int cnt, int base, i32& rpa, i32& rqa, i32& rpb,
                    i32& rqb CHUNK_PARAMS) {
 #ifdef HFTLOB_STAMPS_CHUNK
@@ -1526,13 +1579,14 @@ DEV void run_chunk(Book<S>& B, const int4& x, const int4& y, int cnt, int base, 
 #ifdef HFTLOB_KO_LOOP  // timing knockout builds only (wrong results): no message reaches the book
     todo = 0;
 #endif
-    refresh_best<false>(B);
-    const i32 cpa = B.a.best_p, cqa = B.a.best_q, cpb = B.b.best_p, cqb = B.b.best_q;  // before the chunk
+    refresh_best<false, LZ>(B);
+    const i32 cpa = B.a.best_p, cqa = LZ ? 0 : B.a.best_q, cpb = B.b.best_p, cqb = LZ ? 0 : B.b.best_q;  // before the chunk
     // the best-quote record: a message that sets or recomputes a side's quote writes it into its
     // lane of that side's record (side_rec, at the assignment); the other lanes take the last
     // record before them below (the book, hence that quote, is unchanged since)
     B.a.rm = B.b.rm = 0ull;
-    B.a.rp = B.a.rq = B.b.rp = B.b.rq = 0;
+    B.a.rp = B.b.rp = 0;
+    if (!LZ) B.a.rq = B.b.rq = 0;
 #ifdef HFTLOB_STAMPS_CHUNK
     const unsigned long long tp1 = __builtin_amdgcn_s_memtime();
     acc_pre += tp1 - tp0;
@@ -1546,9 +1600,9 @@ DEV void run_chunk(Book<S>& B, const int4& x, const int4& y, int cnt, int base, 
         do {
             asm volatile("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(k));
             if (RC) B.mi = base + (int)k;
-            if ((i32)B.fl >= 0) process_msg_<false, RC>(B, k, h, x.y, d2, d3, d4, d5, d6, d7);  // (!F_SLOW)
-            else process_msg_<true, RC>(B, k, h, x.y, d2, d3, d4, d5, d6, d7);
-            refresh_best(B, k);
+            if ((i32)B.fl >= 0) process_msg_<false, RC, LZ>(B, k, h, x.y, d2, d3, d4, d5, d6, d7);  // (!F_SLOW)
+            else process_msg_<true, RC, LZ>(B, k, h, x.y, d2, d3, d4, d5, d6, d7);
+            refresh_best<true, LZ>(B, k);
             const u32 kn = ff1(todo);  // (-1 once todo is empty: v_readlane takes the lane's low 6 bits)
             h = rdl(hx, kn); d2 = rdl(x.z, kn); d3 = rdl(x.w, kn);
             d4 = rdl(y.x, kn); d5 = rdl(y.y, kn); d6 = rdl(y.z, kn); d7 = rdl(y.w, kn);
@@ -1563,8 +1617,8 @@ DEV void run_chunk(Book<S>& B, const int4& x, const int4& y, int cnt, int base, 
         const lmask below = ~0ull >> (63 - l);
         const lmask ma = B.a.rm & below, mb = B.b.rm & below;
         const int sa = ma ? 63 - __builtin_clzll(ma) : -1, sb = mb ? 63 - __builtin_clzll(mb) : -1;
-        const i32 gpa = __builtin_amdgcn_ds_bpermute(sa << 2, B.a.rp), gqa = __builtin_amdgcn_ds_bpermute(sa << 2, B.a.rq);
-        const i32 gpb = __builtin_amdgcn_ds_bpermute(sb << 2, B.b.rp), gqb = __builtin_amdgcn_ds_bpermute(sb << 2, B.b.rq);
+        const i32 gpa = __builtin_amdgcn_ds_bpermute(sa << 2, B.a.rp), gqa = LZ ? 0 : __builtin_amdgcn_ds_bpermute(sa << 2, B.a.rq);
+        const i32 gpb = __builtin_amdgcn_ds_bpermute(sb << 2, B.b.rp), gqb = LZ ? 0 : __builtin_amdgcn_ds_bpermute(sb << 2, B.b.rq);
         rpa = sa < 0 ? cpa : gpa;
         rqa = sa < 0 ? cqa : gqa;
         rpb = sb < 0 ? cpb : gpb;
@@ -1583,6 +1637,9 @@ template <int S> DEV void book_bind(Book<S>& B, i32* lds) {
     B.tr.R = B.c.nT;
     B.filt = lds + 12 * B.c.nO + 8 * B.c.nT + PAD_FILT;
     B.filt_ok = false;
+#ifdef HFTLOB_STAMPS_CHUNK
+    B.a.n_resc = B.a.n_rec = B.b.n_resc = B.b.n_rec = 0;
+#endif
     B.a.scr = B.b.scr = B.tr.scr = lds + 12 * B.c.nO + 8 * B.c.nT + PAD_SCR;
     B.vs.init(B.c.nO);
     B.vt.init(B.c.nT);
@@ -1889,6 +1946,20 @@ template <int BAKED> DEV const hftlob_env_cfg& baked_cfg(const hftlob_env_cfg& r
 }
 // (unroll count of the loops over types / agents: all of them when baked, none otherwise)
 template <int BAKED> constexpr int baked_unroll() { return BAKED >= 0 ? HFTLOB_MAX_AGENTS : 1; }
+// some MM type of the config excludes extreme spreads (its reward reads the previous step's whole
+// best-quote arrays, env_step_dev's excl_cfg); a run-time config (BAKED = -1) counts as "may"
+constexpr bool cfg_excl(const hftlob_env_cfg& c) {
+    bool ex = false;
+    for (int t = 0; t < c.n_types; ++t) ex |= c.types[t].kind == HFTLOB_AGENT_MM && c.types[t].exclude_extreme_spreads;
+    return ex;
+}
+template <int BAKED> constexpr bool baked_excl() {
+    if constexpr (BAKED == 0) return cfg_excl(hftlob_baked_cfg_0);
+    else if constexpr (BAKED == 1) return cfg_excl(hftlob_baked_cfg_1);
+    else if constexpr (BAKED == 2) return cfg_excl(hftlob_baked_cfg_2);
+    else if constexpr (BAKED == 3) return cfg_excl(hftlob_baked_cfg_3);
+    else return true;
+}
 
 // ----------------------------------------- reset (MARLEnv.reset_env) device
 // marl_env.py:129-207; BaseLOBEnv.reset_env base_env.py:218-234; agents
@@ -3403,6 +3474,18 @@ DEV bool env_step_dev(const hftlob_env_cfg& c_rt, int key_n, int ek, int e, cons
     constexpr int UNR = baked_unroll<BAKED>();
     const bool emit = !QUIET && emit_rt;
     const bool vals = TALLY || emit;  // the reward values are wanted (the observations: emit)
+    // LAZY, the lazy-volume mode (rescan's LZ): a quiet step of a resident rollout (the kernels run a
+    // quiet step only with a next step to come: keep) whose config is known at compile time to
+    // exclude no extreme spreads, so store_best (below) is false and nothing reads the step's
+    // best-quote volumes: the step keeps none.  Decided at compile time only (LZ_KERNEL: a kernel
+    // that has such steps): with a run-time config store_best is a run-time word, and a choice per
+    // step would double the quiet body or put a test into the message loop.
+#ifdef HFTLOB_NO_LAZY  // (A/B and diagnostic builds only: every step keeps its volumes)
+    constexpr bool LZ_KERNEL = false;
+#else
+    constexpr bool LZ_KERNEL = NFIX > 0 && !RA && !baked_excl<BAKED>();
+#endif
+    constexpr bool LAZY = QUIET && LZ_KERNEL;
     STAMP(t_start);
 #ifdef HFTLOB_STAMPS
     const unsigned long long rt_start = __builtin_amdgcn_s_memrealtime();  // 100 MHz: the in-kernel clock
@@ -3469,7 +3552,7 @@ DEV bool env_step_dev(const hftlob_env_cfg& c_rt, int key_n, int ek, int e, cons
     // (keep is true only in the 100/100 kernel, NFIX > 0, which has no EXE fixed_prices path: that
     // path reads rows M-10..M-1 of the record's arrays, exe_fixed_prices, and runs only where NFIX ==
     // 0, so every step there stores the whole arrays; nfix_kernel keeps fixed_prices configs out)
-    const bool store_best = NFIX == 0 || (!keep | excl_cfg);
+    const bool store_best = LAZY ? false : (NFIX == 0 || (!keep | excl_cfg));  // (LAZY: keep, no excl_cfg)
     // the data window (BaseLOBEnv.get_data_messages, base_env.py:339-369); its
     // first chunk is fetched now, ahead of the agent phase
     i32 dstart = wadd(start_index, wmul(D, step));
@@ -3486,7 +3569,7 @@ DEV bool env_step_dev(const hftlob_env_cfg& c_rt, int key_n, int ek, int e, cons
     if (resident) {  // the book flags as the previous step left them (the cached best quotes are not kept)
         relink_side(B.a, R, B.vs);
         relink_side(B.b, R, B.vs);
-        B.fl = fl_carry | F_STALE_A | F_STALE_B | STALE_ANY;
+        B.fl = (LZ_KERNEL ? fl_carry & ~F_LAZY : fl_carry) | F_STALE_A | F_STALE_B | STALE_ANY;
     } else {
         B.fl = commit_side<true>(B.a, fa, R, B.vs) | commit_side<false>(B.b, fb, R, B.vs) | F_STALE_A | F_STALE_B | STALE_ANY;
         B.fl |= slow_bit(B.fl);
@@ -3719,11 +3802,14 @@ DEV bool env_step_dev(const hftlob_env_cfg& c_rt, int key_n, int ek, int e, cons
     i32* carry = B.filt - PAD_FILT + PAD_CARRY;
     if (!RA && resident) {  // the previous step's quotes and caches: the book is unchanged since
         const i32 v = carry[l & 15];
-        B.a.best_p = rdl(v, 0); B.a.best_q = rdl(v, 1); B.a.xp = rdl(v, 2); B.a.top = rdl(v, 3);
+        B.a.best_p = rdl(v, 0); if (!LAZY) B.a.best_q = rdl(v, 1); B.a.xp = rdl(v, 2); B.a.top = rdl(v, 3);
         B.a.top_p = rdl(v, 4); B.a.top_ts = rdl(v, 5); B.a.top_tns = rdl(v, 6);
-        B.b.best_p = rdl(v, 7); B.b.best_q = rdl(v, 8); B.b.top = rdl(v, 9); B.b.top_p = rdl(v, 10);
+        B.b.best_p = rdl(v, 7); if (!LAZY) B.b.best_q = rdl(v, 8); B.b.top = rdl(v, 9); B.b.top_p = rdl(v, 10);
         B.b.top_ts = rdl(v, 11); B.b.top_tns = rdl(v, 12);
-        B.fl &= ~(F_STALE_A | F_STALE_B | STALE_ANY);
+        // the hand-over from a lazy-volume step to one that keeps volumes (the emitting last step):
+        // words 1 and 8 were not written, so both sides stay stale and the first chunk's refresh
+        // recomputes the quotes, volumes included, from the book (the caches stand)
+        if (!(LZ_KERNEL && !LAZY && (fl_carry & F_LAZY))) B.fl &= ~(F_STALE_A | F_STALE_B | STALE_ANY);
     }
 #endif
 #ifdef HFTLOB_STAMPS_CHUNK
@@ -3768,7 +3854,7 @@ DEV bool env_step_dev(const hftlob_env_cfg& c_rt, int key_n, int ek, int e, cons
 #ifdef HFTLOB_STAMPS_CHUNK
         acc_dec += __builtin_amdgcn_s_memtime() - tc0;
 #endif
-        run_chunk<RC>(B, x, y, cnt, base, rpa, rqa, rpb, rqb CHUNK_ARGS);
+        run_chunk<RC, LAZY>(B, x, y, cnt, base, rpa, rqa, rpb, rqb CHUNK_ARGS);
 #ifdef HFTLOB_STAMPS_CHUNK
         const unsigned long long tc1 = __builtin_amdgcn_s_memtime();
 #endif
@@ -3783,7 +3869,20 @@ DEV bool env_step_dev(const hftlob_env_cfg& c_rt, int key_n, int ek, int e, cons
         const i32 cap = ffill(pa, prev_a), cbp = ffill(pb, prev_b);
         prev_a = rdl(cap, cnt - 1);
         prev_b = rdl(cbp, cnt - 1);
-        if ((row < M) & (store_best | (row == M - 1))) {  // (row M - 1: the one the next step reads)
+        if (LAZY) {
+            // the price words of row M - 1 alone (the next step's old best quotes).  The row's volume
+            // words keep whatever they held, and nobody reads them before they are rewritten: the
+            // next resident step reads the row's prices only; the launch's last step (keep false)
+            // and any step after an auto-reset store the whole arrays before the record leaves the
+            // launch, and the reset rewrites them itself; no type of a LAZY config excludes extreme
+            // spreads (excl_cfg, the one reward that reads the arrays); and the fixed_prices path
+            // that reads rows M-10..M-1 exists only where NFIX == 0
+            if (row == M - 1) {
+                rec[c.off_best_asks + 2 * row] = cap;
+                rec[c.off_best_bids + 2 * row] = cbp;
+            }
+            (void)caq; (void)cbq;
+        } else if ((row < M) & (store_best | (row == M - 1))) {  // (row M - 1: the one the next step reads)
             reinterpret_cast<int2*>(rec + c.off_best_asks)[row] = make_int2(cap, caq);
             reinterpret_cast<int2*>(rec + c.off_best_bids)[row] = make_int2(cbp, cbq);
         }
@@ -3807,10 +3906,12 @@ DEV bool env_step_dev(const hftlob_env_cfg& c_rt, int key_n, int ek, int e, cons
     last_p_b = prev_b;
 #ifndef HFTLOB_NO_CARRY  // (A/B builds only)
     if (!RA && keep) {  // (fresh: run_chunk refreshes both sides after every message)
-        i32 v = B.a.best_p;
-        v = wlane(v, B.a.best_q, 1); v = wlane(v, B.a.xp, 2); v = wlane(v, B.a.top, 3); v = wlane(v, B.a.top_p, 4);
+        i32 v = B.a.best_p;  // (a lazy-volume step leaves words 1 and 8, the volumes, unwritten: F_LAZY below)
+        if (!LAZY) v = wlane(v, B.a.best_q, 1);
+        v = wlane(v, B.a.xp, 2); v = wlane(v, B.a.top, 3); v = wlane(v, B.a.top_p, 4);
         v = wlane(v, B.a.top_ts, 5); v = wlane(v, B.a.top_tns, 6); v = wlane(v, B.b.best_p, 7);
-        v = wlane(v, B.b.best_q, 8); v = wlane(v, B.b.top, 9); v = wlane(v, B.b.top_p, 10);
+        if (!LAZY) v = wlane(v, B.b.best_q, 8);
+        v = wlane(v, B.b.top, 9); v = wlane(v, B.b.top_p, 10);
         v = wlane(v, B.b.top_ts, 11); v = wlane(v, B.b.top_tns, 12);
         if (l < 13) carry[l] = v;
     }
@@ -3835,7 +3936,7 @@ DEV bool env_step_dev(const hftlob_env_cfg& c_rt, int key_n, int ek, int e, cons
     // the book is final: store it now (frees its registers for the rewards).  Not when the
     // auto-reset below rewrites the record anyway, nor while the wave's next step (keep,
     // k_env_rollout) takes the book and trade log from LDS as they are
-    if (keep) fl_carry = B.fl;
+    if (keep) fl_carry = LAZY ? B.fl | F_LAZY : B.fl;
     if (!all & !keep) {
         store_side(B.a, rec + c.off_asks, R, B.vs);
         store_side(B.b, rec + c.off_bids, R, B.vs);
@@ -3982,7 +4083,7 @@ DEV bool env_step_dev(const hftlob_env_cfg& c_rt, int key_n, int ek, int e, cons
 #endif
 #ifdef HFTLOB_STAMPS_CHUNK  // (the chunk build: words 9..12 are the book phase's parts)
         info[9] = (i32)acc_dec; info[10] = (i32)acc_pre; info[11] = (i32)acc_loop; info[12] = (i32)acc_post;
-        info[13] = 0; info[14] = 0;
+        info[13] = (i32)(B.a.n_resc | (B.b.n_resc << 16)); info[14] = (i32)(B.a.n_rec | (B.b.n_rec << 16));  // (per side: a low, b high)
         (void)acc_act; (void)acc_cnl; (void)acc_flt; (void)acc_mmr; (void)acc_exr; (void)acc_obs;
 #else
         info[9] = (i32)acc_act; info[10] = (i32)acc_cnl; info[11] = (i32)acc_flt;

@@ -61,7 +61,12 @@ sub = ["  setup: step keys (LDS row)", "  setup: relink / load book", "  setup: 
 if os.environ.get("ST_CHUNK"):  # the stamps_chunk build: words 9..12 split the book phase
     sub[4:10] = ["    book: loads + decode", "    book: no-op pre-pass", "    book: message loop",
                  "    book: record + ffill + stores", "    -", "    -"]
-for i, n in zip(range(5, 15) if r[:, 5:15].any() else [], sub):
+for i, n in zip(range(5, 13 if os.environ.get("ST_CHUNK") else 15) if r[:, 5:15].any() else [], sub):
     print(f"  {n:32s} median {np.median(r[:, i]):9.0f}  mean {r[:, i].mean():9.0f}")
+if os.environ.get("ST_CHUNK"):  # words 13 / 14: rescans and best-quote records (side_rec), asks low half, bids high
+    for i, n in ((13, "rescans"), (14, "best-quote records (side_rec)")):
+        a, b = r[:, i] & 0xFFFF, (r[:, i] >> 16) & 0xFFFF
+        print(f"  {n + ' per env-step':44s} asks mean {a.mean():7.3f} max {a.max():3d}   bids mean {b.mean():7.3f} "
+              f"max {b.max():3d}   both mean {(a + b).mean():7.3f} median {np.median(a + b):.0f}")
 by_step = np.stack([tot.reshape(T, E).mean(1), top[:, 2].reshape(T, E).mean(1)], 1)
 print("mean cycles by step (total, book loop): " + " ".join(f"{t}:{a:.0f}/{b:.0f}" for t, (a, b) in enumerate(by_step)))
