@@ -657,6 +657,50 @@ int hftlob_ppo_loss(int N, int K, const int* nvec /*[K], host*/, const float* lo
                     double vf_coef, double ent_coef, double* workspace, float* out6 /*[6], device*/,
                     float* d_logits /*[N][S] or NULL*/, float* d_values /*[N] or NULL*/, void* stream);
 
+/* The learner's optimiser step for one net: clipping of the gradients by their global norm
+ * (torch.nn.utils.clip_grad_norm_) and one Adam step (torch.optim.Adam, capturable: the step counters are
+ * float32 device scalars, lr is a float32 device scalar), float32, over up to HFTLOB_ADAM_MAX_TENSORS
+ * parameter tensors.  No weight decay, no amsgrad, no maximize.  tensors is a host array, read at the
+ * call: its pointers and sizes travel to the kernels by value, so they may differ from call to call and
+ * nothing is copied to the device.  Per tensor: p, m (exp_avg), v (exp_avg_sq) [n], updated in place;
+ * g [n], read only (the one difference from clip_grad_norm_, which scales the gradients in place);
+ * step, one float, incremented by 1 before it is used.  Two launches on the caller's stream:
+ *   the norm pass: at most HFTLOB_ADAM_NORM_BLOCKS workgroups walk the chunks of HFTLOB_ADAM_CHUNK
+ *     elements (a tensor's chunks are its own, its last one may be short) in a fixed assignment, sum
+ *     g^2 in double and leave one partial sum each in the workspace; workgroup 0 increments every step;
+ *   the update pass: one workgroup per chunk.  Each folds the partial sums in the same order, and with
+ *       total_norm = sqrt(sum g^2)          coef = min(1, max_norm / (total_norm + 1e-6))
+ *       bc1 = 1 - beta1^step                bc2 = 1 - beta2^step          (the tensor's own step)
+ *       step_size = lr / bc1                (these scalars in double, each rounded to float32 once)
+ *     applies, every operation a separately rounded float32 one, with gc = g coef:
+ *       m = m + (gc - m) (1 - beta1)        v = v beta2 + (1 - beta2) (gc gc)
+ *       p = p - step_size (m / (sqrt(v) / sqrt(bc2) + eps))
+ * No floating-point atomic and a fixed order of every sum: the same inputs give the same bits.
+ * Non-finite gradients propagate as in torch (a NaN norm gives NaN parameters); nothing is checked.
+ * beta1 and beta2 are doubles, as torch holds them: 1 - beta2 formed from a float32 0.999 is off by
+ * 1.3e-5 of itself, which exp_avg_sq would inherit.  total_norm (device, one float) receives the norm
+ * before clipping; it may be NULL.  workspace is HFTLOB_ADAM_WORKSPACE doubles of the caller's, written
+ * before it is read.  The call neither allocates nor synchronises and can be captured in a HIP graph.
+ * HFTLOB_ESHAPE: n_tensors outside 1..HFTLOB_ADAM_MAX_TENSORS, an n < 1 (or more than 2^31 - 1 chunks in
+ * all); HFTLOB_ENULL: a NULL tensors, p, g, m, v, step, lr or workspace; HFTLOB_EINVAL: max_norm not finite
+ * or <= 0, a beta outside [0, 1), eps < 0 (or not finite), a p, g, m or v that is not 16-byte aligned. */
+#define HFTLOB_ADAM_MAX_TENSORS 16
+#define HFTLOB_ADAM_CHUNK 1024        /* elements per workgroup of the update pass */
+#define HFTLOB_ADAM_NORM_BLOCKS 64    /* the most workgroups of the norm pass */
+#define HFTLOB_ADAM_WORKSPACE HFTLOB_ADAM_NORM_BLOCKS   /* doubles: one partial sum per workgroup */
+typedef struct {
+    float* p;          /* [n] the parameter, in/out */
+    const float* g;    /* [n] its gradient, read only */
+    float* m;          /* [n] exp_avg, in/out */
+    float* v;          /* [n] exp_avg_sq, in/out */
+    float* step;       /* one float, in/out: the steps taken */
+    long long n;
+} hftlob_adam_tensor;
+int hftlob_adam_clip(int n_tensors, const hftlob_adam_tensor* tensors /*[n_tensors], host*/,
+                     const float* lr /*device, one float*/, double beta1, double beta2, float eps,
+                     float max_norm, double* workspace /*HFTLOB_ADAM_WORKSPACE doubles*/,
+                     float* total_norm /*device, one float, or NULL*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

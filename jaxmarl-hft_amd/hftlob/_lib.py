@@ -18,6 +18,12 @@ class LaunchInfo(C.Structure):
                 ("rows_alias", C.c_int32), ("lds_bytes", C.c_int32), ("tick_magic", C.c_uint32),
                 ("key_batch", C.c_int32)]
 
+class AdamTensor(C.Structure):
+    """hftlob_adam_tensor (include/hftlob.h): one parameter tensor of hftlob_adam_clip."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("step", C.c_void_p),
+                ("n", C.c_longlong)]
+
+
 class PolicyWeights(C.Structure):
     """hftlob_policy_weights (include/hftlob.h): device pointers of one ActorCriticRNN's parameters."""
     _fields_ = [(n, C.c_void_p) for n in ("w_embed", "b_embed", "w_ih", "b_ih", "w_hh", "b_hh", "w_c1", "b_c1",
@@ -33,7 +39,8 @@ EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob
            "hftlob_env_rollout_actions", "hftlob_env_rollout_eval", "hftlob_eval_tally",
            "hftlob_env_lds_bytes", "hftlob_env_launch_info", "hftlob_env_baked_id", "hftlob_set_baked",
            "hftlob_sample_actions", "hftlob_split_keys", "hftlob_gru_scan_fwd", "hftlob_gru_scan_bwd",
-           "hftlob_policy_step", "hftlob_policy_step_multi", "hftlob_gae", "hftlob_ppo_loss")
+           "hftlob_policy_step", "hftlob_policy_step_multi", "hftlob_gae", "hftlob_ppo_loss",
+           "hftlob_adam_clip")
 
 _lib = None
 
@@ -104,6 +111,9 @@ def lib() -> C.CDLL:
     L.hftlob_ppo_loss.argtypes = [i32, i32, C.POINTER(i32), vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double,
                                   C.c_double, vp, vp, vp, vp, vp]
     L.hftlob_ppo_loss.restype = i32
+    L.hftlob_adam_clip.argtypes = [i32, C.POINTER(AdamTensor), vp, C.c_double, C.c_double, C.c_float, C.c_float, vp,
+                                   vp, vp]
+    L.hftlob_adam_clip.restype = i32
     if L.hftlob_version() != ABI_VERSION:
         raise RuntimeError(f"libhftlob ABI {L.hftlob_version()} != {ABI_VERSION}")
     _lib = L

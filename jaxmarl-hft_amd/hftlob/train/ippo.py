@@ -35,6 +35,8 @@ policy step is one HIP launch per agent type and step (``train.policy.policy_ste
 samples are ``jax.random.categorical`` draws from a carried threefry key, so nothing inside the
 rollout reads torch's generator.  With ``FUSED_LOSS`` the update's GAE is one HIP launch and the
 minibatch step's loss with its gradient three (``train.loss.gae``, ``train.loss.ppo_loss_fused``).
+With ``FUSED_OPT`` the minibatch step's clipping and Adam step are two HIP launches per agent type
+(``train.optim.adam_clip_step``) on capturable Adam's state, so the checkpoints do not change.
 """
 from __future__ import annotations
 
@@ -50,6 +52,7 @@ import torch.nn.functional as F
 from ..env import MARLEnv, split_keys
 from .gru import SUPPORTED_HIDDEN, gru_scan, gru_scan_supported
 from .loss import gae as gae_fused, ppo_loss_fused, ppo_loss_supported
+from .optim import MAX_TENSORS, adam_clip_step, adam_clip_supported, init_adam_state
 from .policy import MAX_ACTIONS, MAX_HEADS, MAX_OBS_DIM, SAMPLE, policy_step_multi_supported, policy_step_net
 
 
@@ -66,7 +69,7 @@ def default_config(**kw) -> Dict:
          "GAE_LAMBDA": [0.85, 0.9], "CLIP_EPS": 0.2, "ENT_COEF": [0.01, 0.01], "VF_COEF": [0.5, 0.5],
          "MAX_GRAD_NORM": [0.5, 0.5], "ANNEAL_LR": [True, True], "NUM_AGENTS_PER_TYPE": [1, 1], "SEED": 2,
          "CUDA_GRAPHS": True, "FUSED_GRU": False, "FUSED_POLICY": False, "FUSED_LOSS": False,
-         "CALC_EVAL": False, "NUM_STEPS_EVAL": None}   # NUM_STEPS_EVAL None: NUM_STEPS
+         "FUSED_OPT": False, "CALC_EVAL": False, "NUM_STEPS_EVAL": None}   # NUM_STEPS_EVAL None: NUM_STEPS
     c.update(kw)
     return c
 
@@ -290,6 +293,16 @@ class IPPOTrainer:
                 if not ppo_loss_supported(n.heads):
                     raise ValueError(f"FUSED_LOSS needs <= {MAX_ACTIONS} actions (in each of <= {MAX_HEADS} heads), "
                                      f"got {n.heads} (agent type {i})")
+        # FUSED_OPT: the minibatch step's global-norm clip and Adam step as two HIP launches
+        # (train.optim.adam_clip_step; GPU only, and there is no other path behind the switch)
+        self.fused_opt = bool(c.get("FUSED_OPT", False))
+        if self.fused_opt:
+            if self.device.type != "cuda":
+                raise ValueError(f"FUSED_OPT needs a GPU device, got {self.device}")
+            for i, n in enumerate(self.nets):
+                if not adam_clip_supported(len(list(n.parameters()))):
+                    raise ValueError(f"FUSED_OPT needs <= {MAX_TENSORS} parameter tensors in a net, got "
+                                     f"{len(list(n.parameters()))} (agent type {i})")
         # CALC_EVAL (:461-482, 876-975): after every update NUM_STEPS_EVAL sampled steps of the current nets
         # in a separate eval env, through the fused policy step and the tally launch (evaluate_policy)
         self.calc_eval = bool(c.get("CALC_EVAL", False))
@@ -311,11 +324,14 @@ class IPPOTrainer:
                                      f"(agent type {i})")
         # HIP-graph minibatch steps: single process on the GPU (the grad all-reduce stays eager)
         self.graphs = bool(c.get("CUDA_GRAPHS", False)) and self.device.type == "cuda" and world == 1
-        if self.graphs:  # capturable Adam: step counter and lr live on the device
+        if self.graphs or self.fused_opt:  # capturable Adam: step counter and lr live on the device
             self.opts = [torch.optim.Adam(n.parameters(), lr=torch.tensor(c["LR"][i], device=self.device), eps=1e-5,
                                           capturable=True) for i, n in enumerate(self.nets)]
         else:
             self.opts = [torch.optim.Adam(n.parameters(), lr=c["LR"][i], eps=1e-5) for i, n in enumerate(self.nets)]
+        if self.fused_opt:  # the state a first torch step would create, which the operator updates in place
+            for opt in self.opts:
+                init_adam_state(opt)
         self._roll = None        # the captured rollout graph (False: not capturable, stays eager)
         self.opt_count = [0] * nt
         self.gen = torch.Generator(device=self.device)
@@ -448,8 +464,11 @@ class IPPOTrainer:
         out[0].backward()
         if self.dist is not None and self.dist.get_world_size() > 1:
             _average_grads(list(net.parameters()), self.dist)
-        torch.nn.utils.clip_grad_norm_(net.parameters(), c["MAX_GRAD_NORM"][i])
-        opt.step()
+        if self.fused_opt:
+            adam_clip_step(opt, c["MAX_GRAD_NORM"][i])
+        else:
+            torch.nn.utils.clip_grad_norm_(net.parameters(), c["MAX_GRAD_NORM"][i])
+            opt.step()
         return torch.stack([x.detach() for x in out])
 
     def _minibatch(self, i: int) -> torch.Tensor:
@@ -555,12 +574,15 @@ class IPPOTrainer:
         ck = _read_checkpoint(path)
         if len(ck["nets"]) != self.n_types:
             raise ValueError(f"{path}: {len(ck['nets'])} agent types, this trainer has {self.n_types}")
+        capturable = self.graphs or self.fused_opt
         for net, opt, sd, od in zip(self.nets, self.opts, ck["nets"], ck["opts"]):
             net.load_state_dict(sd)
             for g in od["param_groups"]:   # capturable Adam keeps lr on the device, the eager one as a float
-                g["capturable"] = self.graphs
-                g["lr"] = torch.tensor(float(g["lr"]), device=self.device) if self.graphs else float(g["lr"])
+                g["capturable"] = capturable
+                g["lr"] = torch.tensor(float(g["lr"]), device=self.device) if capturable else float(g["lr"])
             opt.load_state_dict(od)
+            if self.fused_opt:   # (a checkpoint from before the first step carries no state)
+                init_adam_state(opt)
         self.opt_count = list(ck["opt_count"])
         for st in getattr(self, "_st", []):
             if st is not None:
@@ -635,6 +657,8 @@ def main(argv=None) -> None:
                     help="the rollout's policy step, sample and log-prob as one fused HIP launch")
     ap.add_argument("--fused-loss", action="store_true",
                     help="the update's GAE and PPO loss (with its gradient) as fused HIP launches")
+    ap.add_argument("--fused-opt", action="store_true",
+                    help="the minibatch step's global-norm clip and Adam step as two fused HIP launches")
     ap.add_argument("--calc-eval", action="store_true",
                     help="CALC_EVAL: after every update NUM_STEPS_EVAL sampled steps in a separate eval env (the same "
                          "config, a synthetic day of another seed), logged as avg_reward_eval")
@@ -653,6 +677,8 @@ def main(argv=None) -> None:
         c["FUSED_POLICY"] = True
     if a.fused_loss:
         c["FUSED_LOSS"] = True
+    if a.fused_opt:
+        c["FUSED_OPT"] = True
     if a.calc_eval:
         c["CALC_EVAL"] = True
     cfg = (load_config_from_file(a.env_config) if a.env_config.endswith((".json", ".yaml"))
