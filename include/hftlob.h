@@ -27,6 +27,9 @@
  *   hftlob_env_rollout_eval <- jaxrl/MARL/baseline_eval/baseline_only_JAXMARL.py: the scanned
  *                           _env_step with FixedAction policies and the reduction of its
  *                           trajectory batch (avg_reward, total_dones, info means / stds).
+ *   hftlob_draw_actions / hftlob_env_rollout_eval_drawn <- the same scripts' multi-action FixedAction
+ *                           (baseline_only_JAXMARL.py:58-71) and baseline_JAXMARL.py:367-374
+ *                           RandomPolicy: an action drawn uniformly from a set at every step.
  *   hftlob_sample_actions<- jaxen/Speed_test.py:166-177 (per-env random actions
  *                           via gymnax Discrete.sample = jax.random.randint).
  *   hftlob_split_keys    <- jax.random.split(key, n) (threefry2x32), batched.
@@ -440,6 +443,48 @@ int hftlob_eval_tally(int n_env, int n_agents, int n_steps, int info_words,
                       const uint32_t* float_words /*[n_agents], host*/,
                       double* stats /*[n_env][n_agents][HFTLOB_EVAL_WORDS], in/out*/, void* stream);
 
+/* The drawn actions of a uniform baseline policy for a batch of actors, as one launch — replaces the
+ * per-step pi.sample of the reference's multi-action FixedAction (baseline_eval/
+ * baseline_only_JAXMARL.py:58-71, 305; baseline_JAXMARL.py:381-394: a distrax.Categorical with the same
+ * probability on each listed action) and of its RandomPolicy (baseline_JAXMARL.py:367-374: uniform
+ * over the action space), for a caller who steps the env himself (hftlob/evaluate.py evaluate_policy).
+ * actions[b] is the smallest a with bit a of `allowed` set that maximises g[b][a], where
+ * g = jax.random.gumbel(key, (n_actors, n_actions)) under the partitionable threefry in float32 (the
+ * random word of element (b, a) is at counter (0, b * n_actions + a)): jax.random.categorical on logits
+ * 0 on the allowed actions and -inf elsewhere.  A mask of exactly one bit draws nothing and gives that
+ * action.  hftlob/evaluate.py draw_actions_reference is the definition on the CPU; the float32
+ * logarithms may differ from the host's in the last place, so a row whose two largest allowed noises
+ * are closer than that is not pinned.  (The reference adds log(1 / k) to the k allowed logits, which
+ * moves no argmax but an exact float tie; no JAX-produced vector pins the draw.)
+ * key uint32 [2] on the device.  32 lanes per actor: one threefry block and two logs per (b, a).
+ * The call neither allocates nor synchronises and can be captured in a hipGraph.
+ * HFTLOB_EINVAL: a NULL pointer; n_actors < 1; n_actions outside 1..32; an empty mask or mask bits
+ * >= n_actions; n_actors * n_actions > 2^32 (the counter's low word). */
+int hftlob_draw_actions(int n_actors, int n_actions, uint32_t allowed, const uint32_t* key /*[2], device*/,
+                        int32_t* actions /*[n_actors]*/, void* stream);
+
+/* hftlob_env_rollout_eval with the actions of uniform baseline policies drawn inside the launch: at
+ * the top of every step each env's wave draws its own agents' action words.  Agent j of type i in env
+ * e is actor b = e * n_agents_i + j of that type's n_env * n_agents_i actors, and its action at step t
+ * is what hftlob_draw_actions gives actor b under draw_keys[t][i] and allowed[i].
+ * draw_keys uint32 [n_steps][n_types][2], device; allowed uint32 [n_types], HOST, read at the call and
+ * passed to the kernel by value (a mask of one bit is a fixed action); actions_out int32 [n_steps]
+ * [n_env][action_words], device, receives the drawn words, NULL skips the stores.
+ * The state, `out` and `stats` are bit for bit those of hftlob_env_rollout_eval over the same keys and
+ * those [n_steps][n_env][action_words] actions.  The kernel instantiation follows the rule of the other
+ * env launches (hftlob_env_launch_info, apart from key_batch); the call neither allocates nor
+ * synchronises and can be captured in a hipGraph.
+ * HFTLOB_EINVAL: prng_partitionable off (the draw is built for the partitionable threefry only); a
+ * type with action_width != 1 (a MultiDiscrete space), n_actions outside 1..32, an empty mask or mask
+ * bits >= n_actions; n_env * n_agents_i * n_actions_i > 2^32.  Sizes and NULL pointers are refused as
+ * hftlob_env_rollout_eval refuses them. */
+int hftlob_env_rollout_eval_drawn(const hftlob_env_cfg* cfg /*[host]*/, int n_env, int n_steps, const uint32_t* keys,
+                                  const uint32_t* draw_keys /*[n_steps][n_types][2]*/,
+                                  const uint32_t* allowed /*[n_types], host*/,
+                                  int32_t* actions_out /*[n_steps][n_env][action_words] or NULL*/,
+                                  const int32_t* msg_data, const int32_t* init_states, int32_t* state, double* stats,
+                                  const hftlob_step_out* out /*[host] struct*/, void* stream);
+
 /* Creates the library streams / events hftlob_env_rollout_sampled needs for n_slices
  * slices on the device of `stream` (host-only; idempotent). */
 int hftlob_rollout_prepare(int n_slices, void* stream);
@@ -452,7 +497,7 @@ int hftlob_rollout_prepare(int n_slices, void* stream);
 int hftlob_env_lds_bytes(const hftlob_env_cfg* cfg /*[host]*/);
 
 /* Which kernel instantiation hftlob_env_step / hftlob_env_rollout_sampled /
- * hftlob_env_rollout_actions / hftlob_env_rollout_eval launch for this config (key_batch: the
+ * hftlob_env_rollout_actions / hftlob_env_rollout_eval / hftlob_env_rollout_eval_drawn launch for this config (key_batch: the
  * sampled rollout only), and
  * the launch-derived constants they pass it (host-only, no device call).  Tests use it to assert which code path a parity case ran; it replaces nothing in the reference.
  *   slot_sets     register sets per lane (1, 2 or 4: n_orders / n_trades up to 64 / 128 / 256)

@@ -27,6 +27,7 @@
 #include <limits.h>
 
 #include "../../include/hftlob.h"
+#include "hftlob_draw.h"  // draw_action (k_env_rollout_eval_drawn)
 #include "hftlob_internal.h"
 // the env configs the package ships, as compile-time constants (tools/gen_baked_cfg.py)
 #define HFTLOB_BAKED_QUAL static
@@ -3437,7 +3438,9 @@ DEV void tally_store(double* row, const TallyLane& t, float rew, const i32 (&iw)
 // NFIX > 0: nOrders == nTrades == NFIX known at compile time (the reference's
 // 100/100 default), which folds the slot-validity masks away.
 template <int S, int NFIX, bool RC, bool RA = false, bool QUIET = false, int PK = -1, bool TALLY = false,
-          int BAKED = -1>
+          int BAKED = -1, bool DRAWN = false>
+// DRAWN: the agents' actions come in `drawn`, lane ag holding agent ag's one action word
+// (k_env_rollout_eval_drawn, Discrete spaces only); actions_io is not read.
 // BAKED: the config is a baked one (baked_cfg above); c_rt then gives the run-time words only.
 // RC: cancel_mode 2/3 (the random cancel fallback of the engine).  RA: the agent rows live in the
 // trade log (lds_map).  QUIET: a step whose outputs are never emitted (emit = false at compile
@@ -3469,7 +3472,7 @@ DEV bool env_step_dev(const hftlob_env_cfg& c_rt, int key_n, int ek, int e, cons
                       i32* __restrict__ info_out, i32* __restrict__ obs_raw_out, i32* __restrict__ msgs_out,
                       i32* __restrict__ debug_out, i32* lds, bool resident, bool keep, u32& fl_carry,
                       const i32* pre_keys = nullptr, bool emit_rt = true, double* __restrict__ stats = nullptr,
-                      int act_e = -1) {
+                      int act_e = -1, i32 drawn = 0) {
     const hftlob_env_cfg& c = baked_cfg<BAKED>(c_rt);
     constexpr int UNR = baked_unroll<BAKED>();
     const bool emit = !QUIET && emit_rt;
@@ -3602,7 +3605,9 @@ DEV bool env_step_dev(const hftlob_env_cfg& c_rt, int key_n, int ek, int e, cons
                 aw += w;
                 i32 act, av[4] = {0, 0, 0, 0};
                 if (NFIX > 0 || w == 1) {  // the 100/100 kernel is launched for Discrete spaces only
-                    if (master) {  // Speed_test.py:166-177, sampled by step_keys
+                    if constexpr (DRAWN) {
+                        act = rdl(drawn, ag);
+                    } else if (master) {  // Speed_test.py:166-177, sampled by step_keys
                         act = rdl(SK.acts, 32 + ag);
                         if (aio && l == 0) aio[0] = act;
                     } else {
@@ -4455,6 +4460,95 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout_eval(hftlob_env_cfg c, in
 #endif
 }
 
+// Drawn-baseline evaluation (hftlob_env_rollout_eval_drawn): k_env_rollout_eval whose actions are
+// drawn by the env's own wave at the top of every step instead of read.  Agent j of type i in env e
+// is actor b = e * n_agents_i + j of the type, and its action is hftlob_draw.h's draw_action under the
+// step's key of the type (draw_keys [n_steps][n_types][2]) and the type's allowed mask (am, by value):
+// what hftlob_draw_actions gives for the type's n_env * n_agents_i actors.  Two actors per pass, one
+// per half of the wave; the drawn words stay in a register, lane ag holding agent ag's (the step body's
+// DRAWN mode reads them with v_readlane), and go out to actions_out [n_steps][n_env][action_words]
+// where that is not NULL: the wave never reads them back, so the store needs no ordering.  Every type
+// has a Discrete space here (action_words == n_agents; the launch code refuses the others).
+struct DrawMasks {
+    u32 m[HFTLOB_MAX_TYPES];
+};
+template <int S, int NFIX, bool RC, bool RA = false>
+__global__ __launch_bounds__(64, 4) void k_env_rollout_eval_drawn(hftlob_env_cfg c, int n_env, int n_steps,
+                                                               const u32* __restrict__ keys,
+                                                               const u32* __restrict__ draw_keys, DrawMasks am,
+                                                               i32* __restrict__ actions_out,
+                                                               const i32* __restrict__ msg_data,
+                                                               const i32* __restrict__ init_states,
+                                                               i32* __restrict__ state, double* __restrict__ stats,
+                                                               hftlob_step_out out) {
+    one_wave();
+    extern __shared__ __attribute__((aligned(16))) i32 lds[];
+    const int e = blockIdx.x;
+    if (e >= n_env) return;
+    Key mk{0u, 0u};  // (env_step_dev's master-key reference: never read with master = false)
+    kcfg_t* kp = (kcfg_t*)__builtin_amdgcn_kernarg_segment_ptr();
+    bool resident = false;  // (the 100/100 instantiation only, as in k_env_rollout)
+    u32 fl = 0;
+#ifndef HFTLOB_NO_BALANCE
+    const unsigned long long bal_r0 = __builtin_amdgcn_s_memrealtime();
+    const u32 bal_hwid = __builtin_amdgcn_s_getreg(0xF804), bal_xcc = __builtin_amdgcn_s_getreg(0x7814);
+    u32 bal_slot;
+    unsigned long long* bal_row = wave_row(bal_hwid, bal_xcc, bal_slot);
+#endif
+    // one step, as in k_env_rollout_eval, after the draw of its actions
+    auto step = [&](auto Q, int t) {
+        constexpr bool QT = decltype(Q)::value;
+        kcfg_t* cp = kp;
+        i32* st = state;
+        const i32* md = msg_data;
+        const i32* is = init_states;
+        double* sp = stats;
+        asm volatile("" : "+s"(cp), "+s"(st), "+s"(md), "+s"(is), "+s"(sp));
+        const hftlob_env_cfg& cc = *(const hftlob_env_cfg*)cp;
+        const int l = lane_id();
+        i32 drawn = 0;
+        {
+            const u32* dk = draw_keys + (size_t)t * cc.n_types * 2;
+            int ag0 = 0;
+            for (int ty = 0; ty < cc.n_types; ++ty) {
+                const int n = cc.types[ty].n_agents, A = cc.types[ty].n_actions;
+                const u32 k0 = dk[2 * ty], k1 = dk[2 * ty + 1];
+                u32 m = am.m[0];  // (a select chain: an indexed by-value array would live in scratch memory)
+#pragma unroll
+                for (int k = 1; k < HFTLOB_MAX_TYPES; ++k) m = ty == k ? am.m[k] : m;
+                for (int j0 = 0; j0 < n; j0 += 2) {
+                    const int j = min(j0 + (l >> 5), n - 1);  // (an odd n's last pass: both halves draw agent n - 1)
+                    const i32 a = hftlob_draw::draw_action(k0, k1, (u32)e * (u32)n + (u32)j, A, m, l);
+                    const i32 a0 = rdl(a, 0), a1 = rdl(a, 32);
+                    if (l == ag0 + j0) drawn = a0;
+                    if ((l == ag0 + j0 + 1) & (j0 + 1 < n)) drawn = a1;
+                }
+                ag0 += n;
+            }
+            if (actions_out && l < cc.n_agents) actions_out[((size_t)t * n_env + e) * cc.action_words + l] = drawn;
+        }
+        const bool ox = !QT;  // (the optional outputs: written by the emitted step only)
+        const bool reset = env_step_dev<S, NFIX, RC, RA, QT, /*PK=*/0, /*TALLY=*/true, /*BAKED=*/-1, /*DRAWN=*/true>(
+            cc, n_env, e, e, keys + (size_t)t * n_env * 2, false, mk, nullptr, md, is, st, out.obs, out.rewards,
+            out.done_all, out.dones, ox ? out.info : nullptr, ox ? out.obs_raw : nullptr, ox ? out.msgs : nullptr,
+            ox ? out.debug : nullptr, lds, NFIX > 0 && resident, NFIX > 0 && t + 1 < n_steps, fl, nullptr, !QT, sp, -1,
+            drawn);
+        resident = uni(!reset) != 0;  // (an auto-reset rewrote the record: the next step loads the book from it)
+#ifndef HFTLOB_NO_BALANCE
+        if ((t + 1 < n_steps) && ((t % HFTLOB_BALANCE_EVERY) == 0) && (n_env > HFTLOB_BALANCE_MIN_ENVS))
+            balance_prio(bal_row, bal_slot, bal_r0, t + 1, n_steps - t - 1);
+#endif
+    };
+    int t = 0;
+#pragma unroll 1
+    for (; t + 1 < n_steps; ++t) step(std::integral_constant<bool, true>{}, t);
+    step(std::integral_constant<bool, false>{}, t);
+#ifndef HFTLOB_NO_BALANCE
+    if (lane_id() == 0) __hip_atomic_store(bal_row + bal_slot, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
+                                           HFTLOB_PRIO_SCOPE);
+#endif
+}
+
 // ==================================================== K3/K4: PRNG kernels
 #if !defined(HFTLOB_INST)  // (non-template kernels: the main translation unit only)
 __global__ void k_sample_actions(hftlob_env_cfg c, int n_env, const u32* __restrict__ keys, i32* __restrict__ actions) {
@@ -4487,7 +4581,8 @@ __global__ void k_split_keys(int n_env, int n, int part, const u32* __restrict__
 #endif  // !HFTLOB_INST
 
 // ============================================ kernel variants (parallel build)
-// The env kernels (k_env_step, k_env_rollout, k_env_rollout_actions, k_env_rollout_eval) exist in these
+// The env kernels (k_env_step, k_env_rollout, k_env_rollout_actions, k_env_rollout_eval,
+// k_env_rollout_eval_drawn) exist in these
 // (S, NFIX, RC, RA) variants and no others: the general-size kernels at 1 / 2 / 4 slot sets without
 // and with the random cancel, and the 100/100 kernel without and with the rows-in-trades layout.
 // env_variant (below) picks one for a config; the declarations and the dispatch come from this list.
@@ -4512,6 +4607,8 @@ constexpr bool is_variant(int S, int NFIX, bool RC, bool RA) {
 #define HFTLOB_RACT_ARGS hftlob_env_cfg, int, int, int, const u32*, const i32*, const i32*, const i32*, i32*, hftlob_step_out
 #define HFTLOB_REVAL_ARGS hftlob_env_cfg, int, int, int, const u32*, const i32*, const i32*, const i32*, i32*, double*, \
                           hftlob_step_out
+#define HFTLOB_REVALD_ARGS hftlob_env_cfg, int, int, const u32*, const u32*, DrawMasks, i32*, const i32*, const i32*, i32*, \
+                           double*, hftlob_step_out
 #define HFTLOB_LISTED(SS, NF, RC, RA) static_assert(is_variant(SS, NF, RC, RA), "not in HFTLOB_VARIANTS");
 #define HFTLOB_STEP(P, SS, NF, RC, RA) \
     HFTLOB_LISTED(SS, NF, RC, RA) P template __global__ void k_env_step<SS, NF, RC, RA>(HFTLOB_STEP_ARGS);
@@ -4531,12 +4628,18 @@ constexpr bool is_variant(int S, int NFIX, bool RC, bool RA) {
     HFTLOB_LISTED(SS, NF, RC, RA) P template __global__ void k_env_rollout_actions<SS, NF, RC, RA>(HFTLOB_RACT_ARGS);
 #define HFTLOB_REVAL(P, SS, NF, RC, RA) \
     HFTLOB_LISTED(SS, NF, RC, RA) P template __global__ void k_env_rollout_eval<SS, NF, RC, RA>(HFTLOB_REVAL_ARGS);
+#define HFTLOB_REVALD(P, SS, NF, RC, RA) \
+    HFTLOB_LISTED(SS, NF, RC, RA) P template __global__ void k_env_rollout_eval_drawn<SS, NF, RC, RA>(HFTLOB_REVALD_ARGS);
 // The Makefile compiles this file HFTLOB_NPARTS + 1 times: part k (HFTLOB_INST = k) instantiates the
 // kernels HFTLOB_PARTk names, the main translation unit (no HFTLOB_INST) declares every listed
 // variant's kernels extern and holds the small kernels and the C ABI.  Which part a kernel builds
 // in only balances the parallel build (part 1 stays the metric kernel alone: `make asm`); a listed
 // kernel that no part instantiates fails the link (-z defs).
-#define HFTLOB_NPARTS 19
+#define HFTLOB_NPARTS 23
+#define HFTLOB_PART20(P) HFTLOB_REVALD(P, 2, 100, false, false) HFTLOB_REVALD(P, 1, 0, false, false)
+#define HFTLOB_PART21(P) HFTLOB_REVALD(P, 2, 100, false, true) HFTLOB_REVALD(P, 1, 0, true, false)
+#define HFTLOB_PART22(P) HFTLOB_REVALD(P, 2, 0, false, false) HFTLOB_REVALD(P, 2, 0, true, false)
+#define HFTLOB_PART23(P) HFTLOB_REVALD(P, 4, 0, false, false) HFTLOB_REVALD(P, 4, 0, true, false)
 #define HFTLOB_PART18(P) HFTLOB_ROLL_BAKED(P, 0, 1)
 #define HFTLOB_PART19(P) HFTLOB_ROLL_BAKED(P, 1, 0)
 #define HFTLOB_PART1(P) HFTLOB_ROLL_KB(P, 1)
@@ -4567,7 +4670,7 @@ HFTLOB_CAT(HFTLOB_PART, HFTLOB_INST)()
 #if !defined(HFTLOB_SINGLE_TU)
 #define HFTLOB_X(SS, NF, RC, RA)                                                                                   \
     HFTLOB_STEP(extern, SS, NF, RC, RA) HFTLOB_ROLL(extern, SS, NF, RC, RA) HFTLOB_RACT(extern, SS, NF, RC, RA) \
-    HFTLOB_REVAL(extern, SS, NF, RC, RA)
+    HFTLOB_REVAL(extern, SS, NF, RC, RA) HFTLOB_REVALD(extern, SS, NF, RC, RA)
 HFTLOB_VARIANTS(HFTLOB_X)
 #undef HFTLOB_X
 HFTLOB_ROLL_KB(extern, 1) HFTLOB_ROLL_KB(extern, 0)
@@ -5119,6 +5222,39 @@ int hftlob_env_rollout_eval(const hftlob_env_cfg* cfg, int n_env, int n_steps, c
             return k_env_rollout_eval<decltype(V)::S, decltype(V)::NFIX, decltype(V)::RC, decltype(V)::RA>;
         },
         n_steps, actions_fixed != 0 ? 1 : 0, keys, actions, msg_data, init_states, state, stats, *out);
+}
+
+int hftlob_env_rollout_eval_drawn(const hftlob_env_cfg* cfg, int n_env, int n_steps, const uint32_t* keys,
+                                  const uint32_t* draw_keys, const uint32_t* allowed, int32_t* actions_out,
+                                  const int32_t* msg_data, const int32_t* init_states, int32_t* state, double* stats,
+                                  const hftlob_step_out* out, void* stream) {
+    int rc = check_env(cfg);
+    if (rc) return rc;
+    if (n_env < 1 || n_steps < 1) return fail(HFTLOB_ESHAPE, "n_env and n_steps must be >= 1");
+    if (!keys || !draw_keys || !allowed || !msg_data || !init_states || !state || !stats || !out)
+        return fail(HFTLOB_ENULL, "null array");
+    if (!out->obs || !out->rewards || !out->done_all || !out->dones) return fail(HFTLOB_ENULL, "null output");
+    if (!cfg->prng_partitionable)
+        return fail(HFTLOB_EINVAL, "rollout_eval_drawn: prng_partitionable is off; the draw is built for the partitionable threefry only");
+    DrawMasks am;
+    for (int t = 0; t < HFTLOB_MAX_TYPES; ++t) am.m[t] = 1u;
+    for (int t = 0; t < cfg->n_types; ++t) {
+        const hftlob_agent_type_cfg& tc = cfg->types[t];
+        if (tc.action_width != 1) return fail(HFTLOB_EINVAL, "rollout_eval_drawn: a type with action_width != 1 (MultiDiscrete)");
+        if (tc.n_actions < 1 || tc.n_actions > 32) return fail(HFTLOB_EINVAL, "rollout_eval_drawn: a type's n_actions is outside 1..32");
+        if (allowed[t] == 0u) return fail(HFTLOB_EINVAL, "rollout_eval_drawn: a type's allowed mask is empty");
+        if (tc.n_actions < 32 && (allowed[t] >> tc.n_actions) != 0u)
+            return fail(HFTLOB_EINVAL, "rollout_eval_drawn: a type's allowed mask has bits >= n_actions");
+        if ((long long)n_env * tc.n_agents * tc.n_actions > 0x100000000LL)
+            return fail(HFTLOB_EINVAL, "rollout_eval_drawn: n_env * n_agents * n_actions of a type is past the 32-bit counter");
+        am.m[t] = allowed[t];
+    }
+    return env_launch(
+        cfg, n_env, stream,
+        [](auto V, const Variant&) {
+            return k_env_rollout_eval_drawn<decltype(V)::S, decltype(V)::NFIX, decltype(V)::RC, decltype(V)::RA>;
+        },
+        n_steps, keys, draw_keys, am, actions_out, msg_data, init_states, state, stats, *out);
 }
 
 int hftlob_sample_actions(const hftlob_env_cfg* cfg, int n_env, const uint32_t* keys, int32_t* actions, void* stream) {

@@ -34,6 +34,7 @@
 // requested before the previous stage's epilogue and barrier.
 #include <stdint.h>
 
+#include "hftlob_draw.h"  // threefry_bits, gumbel_from_bits
 #include "hftlob_tile.h"  // f32x4, ld4 / splat, sigmoidf_, TILE and the MFMA operand maps
 
 namespace {
@@ -43,35 +44,9 @@ typedef uint32_t u32;
 constexpr int PF = 2;     // weight chunks in flight per stream
 constexpr int DMAX = 64;  // obs columns in LDS (D <= 64, zero-padded)
 
-__device__ __forceinline__ u32 rotl32(u32 x, int r) { return (x << r) | (x >> (32 - r)); }
-
-// threefry2x32 with 20 rounds (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3"), as JAX
-// runs it: returns y0 ^ y1, the partitionable random_bits word of counter (x0, x1)
-__device__ __forceinline__ u32 threefry_bits(u32 k0, u32 k1, u32 x0, u32 x1) {
-    const u32 ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
-    const int rot[2][4] = {{13, 15, 26, 6}, {17, 29, 16, 24}};
-    x0 += ks[0];
-    x1 += ks[1];
-#pragma unroll
-    for (int i = 1; i <= 5; ++i) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            x0 += x1;
-            x1 = rotl32(x1, rot[(i - 1) & 1][j]) ^ x0;
-        }
-        x0 += ks[i % 3];
-        x1 += ks[(i + 1) % 3] + (u32)i;
-    }
-    return x0 ^ x1;
-}
-
-// jax.random.gumbel's float32 draw from one random word
-__device__ __forceinline__ float gumbel_from_bits(u32 bits) {
-    const float tiny = 1.17549435e-38f;  // float32's smallest normal
-    const float f = __uint_as_float((bits >> 9) | 0x3f800000u) - 1.0f;
-    const float u = fmaxf(tiny, f * (1.0f - tiny) + tiny);
-    return -logf(-logf(u));
-}
+// the partitionable threefry's random word and jax.random.gumbel's float32 draw from it
+using hftlob_draw::gumbel_from_bits;
+using hftlob_draw::threefry_bits;
 
 // the first PF chunks of N weight rows (wp[n] is the lane's row, already at its quarter's 8 q)
 template <int N>

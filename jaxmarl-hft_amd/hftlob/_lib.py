@@ -37,6 +37,7 @@ EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob
            "hftlob_book_process_depth", "hftlob_env_reset",
            "hftlob_env_step", "hftlob_env_step_sampled", "hftlob_env_rollout_sampled", "hftlob_rollout_prepare",
            "hftlob_env_rollout_actions", "hftlob_env_rollout_eval", "hftlob_eval_tally",
+           "hftlob_draw_actions", "hftlob_env_rollout_eval_drawn",
            "hftlob_env_lds_bytes", "hftlob_env_launch_info", "hftlob_env_baked_id", "hftlob_set_baked",
            "hftlob_sample_actions", "hftlob_split_keys", "hftlob_gru_scan_fwd", "hftlob_gru_scan_bwd",
            "hftlob_policy_step", "hftlob_policy_step_multi", "hftlob_gae", "hftlob_ppo_loss",
@@ -82,6 +83,11 @@ def lib() -> C.CDLL:
     L.hftlob_env_rollout_eval.restype = i32
     L.hftlob_eval_tally.argtypes = [i32, i32, i32, i32, vp, vp, vp, C.POINTER(C.c_uint32), vp, vp]
     L.hftlob_eval_tally.restype = i32
+    L.hftlob_draw_actions.argtypes = [i32, i32, C.c_uint32, vp, vp, vp]
+    L.hftlob_draw_actions.restype = i32
+    L.hftlob_env_rollout_eval_drawn.argtypes = [C.POINTER(EnvCfg), i32, i32, vp, vp, C.POINTER(C.c_uint32), vp, vp, vp, vp,
+                                                vp, C.POINTER(StepOut), vp]
+    L.hftlob_env_rollout_eval_drawn.restype = i32
     L.hftlob_rollout_prepare.argtypes = [i32, vp]
     L.hftlob_rollout_prepare.restype = i32
     L.hftlob_env_lds_bytes.argtypes = [C.POINTER(EnvCfg)]

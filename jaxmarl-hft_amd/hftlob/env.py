@@ -664,6 +664,54 @@ class MARLEnv:
                   _lib.ptr(state.buf), _lib.ptr(stats), C.byref(o["struct"]))
         return self._results(o, state, E) + (stats,)
 
+    def rollout_eval_drawn(self, key: torch.Tensor, state: MultiAgentState, draw_keys: torch.Tensor, allowed,
+                           params: MultiAgentParams, stats: Optional[torch.Tensor] = None,
+                           actions_out: Optional[torch.Tensor] = None):
+        """:meth:`rollout_eval` whose actions are drawn inside the launch (hftlob_env_rollout_eval_drawn):
+        at every step each agent of type i takes the smallest allowed action that maximises its
+        Gumbel noise under that step's key of the type, :func:`hftlob.evaluate.draw_actions` of the
+        type's E * n_i actors (env-major), so a uniform baseline policy costs one launch per chunk of
+        steps as a fixed action does.  Returns :meth:`rollout_eval`'s tuple, bit for bit what it gives
+        over the same keys and those actions.
+        key: uint32 / int32 [T, E, 2].  draw_keys: uint32 / int32 [T, n_types, 2] on this env's device.
+        allowed: one bit mask per agent type (host ints; bit a set = action a may be drawn; a mask
+        of one bit is a fixed action).  Every type must have a Discrete space of at most 32 actions
+        and the env partitionable keys.  actions_out: int32 [T, E, action_words] on the device to
+        receive the drawn actions, or None."""
+        if key.dtype not in (torch.int32, torch.uint32) or key.dim() != 3 or key.shape[2] != 2:
+            raise ValueError("key must be a uint32/int32 tensor [T, E, 2] (one threefry key per step and env)")
+        T, E = int(key.shape[0]), int(key.shape[1])
+        if T < 1 or E < 1:
+            raise ValueError("rollout_eval_drawn needs T >= 1 steps of E >= 1 envs")
+        if state.buf.shape[0] != E:
+            raise ValueError(f"key is for {E} envs, the state holds {state.buf.shape[0]}")
+        n_types = len(self.multi_agent_config.number_of_agents_per_type)
+        dev = state.buf.device
+        if (not isinstance(draw_keys, torch.Tensor) or draw_keys.dtype not in (torch.int32, torch.uint32)
+                or tuple(draw_keys.shape) != (T, n_types, 2) or draw_keys.device != dev
+                or not draw_keys.is_contiguous()):
+            raise ValueError(f"draw_keys must be a contiguous uint32/int32 tensor [{T}, {n_types}, 2] on {dev}")
+        masks = [int(m) for m in allowed]
+        if len(masks) != n_types or any(m < 0 or m > 0xFFFFFFFF for m in masks):
+            raise ValueError(f"allowed must hold one 32-bit mask per agent type ({n_types})")
+        if actions_out is not None and (not isinstance(actions_out, torch.Tensor) or actions_out.dtype != torch.int32
+                                        or tuple(actions_out.shape) != (T, E, self.action_words)
+                                        or actions_out.device != dev or not actions_out.is_contiguous()):
+            raise ValueError(f"actions_out must be a contiguous int32 [{T}, {E}, {self.action_words}] tensor on {dev}")
+        shape = (E, self.num_agents, _lib.EVAL_WORDS)
+        if stats is None:
+            stats = torch.zeros(shape, dtype=torch.float64, device=self.device)
+        elif (not isinstance(stats, torch.Tensor) or stats.dtype != torch.float64 or tuple(stats.shape) != shape
+              or stats.device != dev or not stats.is_contiguous()):
+            raise ValueError(f"stats must be a contiguous float64 {list(shape)} tensor on {dev}")
+        keys = key.to(self.device).contiguous()
+        o = self._outputs(E)
+        self._abi("hftlob_env_rollout_eval_drawn", C.byref(self.cfg_c), E, T, _lib.ptr(keys),
+                  _lib.ptr(draw_keys), (C.c_uint32 * n_types)(*masks), _lib.ptr(actions_out),
+                  _lib.ptr(params.loaded_params.message_data), _lib.ptr(params.loaded_params.init_states_array),
+                  _lib.ptr(state.buf), _lib.ptr(stats), C.byref(o["struct"]))
+        return self._results(o, state, E) + (stats,)
+
     def _results_steps(self, o, state, T: int, E: int):
         """_results of per-step buffers [T, E, ...]: a leading [T] on obs / rewards / dones."""
         flat = {k: (v.reshape((T * E,) + tuple(v.shape[2:])) if isinstance(v, torch.Tensor) else v)

@@ -22,6 +22,13 @@ into per-agent accumulators instead of writing a trajectory.
   ``--checkpoint PATH --baseline-actions 4,2 --combinations``).  The reference's per-combination
   agent-config overrides (BASELINE_CONFIGS, get_ma_config) are not covered: one env config serves
   every combination.
+* :class:`Uniform` is the reference's stochastic baseline as a policy entry: its FixedAction with
+  several actions (one of them drawn uniformly at every step) and, as ``Uniform.all()``, its
+  RandomPolicy (baseline_JAXMARL.py:367-394).  :func:`draw_actions_reference` defines the draw in
+  numpy, :func:`draw_actions` is its launch (hftlob_draw_actions), :func:`evaluate_baseline` is
+  :func:`evaluate_fixed_actions` for fixed and drawn types in any mix, drawing inside the persistent
+  launch (``--uniform-actions 1+2+3,all``); :func:`evaluate_policy` and
+  :func:`evaluate_combinations` take a ``Uniform`` where they take a fixed action.
 
 Plotting (the rest of baseline_eval/) is not covered.
 """
@@ -33,8 +40,10 @@ import json
 import math
 import os
 import sys
-from typing import Dict, List, Optional, Sequence
+from dataclasses import dataclass
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -238,6 +247,164 @@ class EvalStats:
         return {"total_dones": self.total_dones(), "types": types}
 
 
+MAX_DRAW_ACTIONS = 32   # the actions of a drawn type: one 32-bit mask, one lane per action
+
+
+def _several_fixed_actions(t: int, n: int) -> NotImplementedError:
+    return NotImplementedError(
+        f"agent type {t}: {n} fixed actions; the reference draws one of them uniformly per step "
+        "(JAX's categorical), which is not implemented for a bare list: give one action per agent type, or "
+        "Uniform([...]) for the draw")
+
+
+@dataclass(frozen=True)
+class Uniform:
+    """A policy entry: at every step each agent of the type takes one of ``actions``, drawn uniformly
+    (:func:`draw_actions_reference` is the draw).  ``Uniform([1, 2, 3])`` is the reference's
+    FixedAction with several actions (baseline_eval/baseline_only_JAXMARL.py:58-71),
+    ``Uniform.all()`` its RandomPolicy (baseline_JAXMARL.py:367-374): every action of the type's space,
+    filled in when the entry meets an env.  ``Uniform([a])`` is the fixed action ``a``."""
+    actions: Optional[Tuple[int, ...]]
+
+    def __post_init__(self):
+        if self.actions is None:
+            return
+        if isinstance(self.actions, (str, bytes)) or not isinstance(self.actions, Iterable):
+            raise TypeError(f"Uniform: actions must be a list of ints, got {type(self.actions).__name__}")
+        acts = tuple(self.actions)
+        if not acts:
+            raise ValueError("Uniform: an empty list of actions (Uniform.all() is every action of the space)")
+        for a in acts:
+            if isinstance(a, bool) or not isinstance(a, int):
+                raise TypeError(f"Uniform: an action must be an int, got {type(a).__name__} {a!r}")
+            if a < 0:
+                raise ValueError(f"Uniform: a negative action {a}")
+        if len(set(acts)) != len(acts):
+            raise ValueError(f"Uniform: duplicate actions in {list(acts)} (a weighted set is not covered)")
+        object.__setattr__(self, "actions", acts)
+
+    @classmethod
+    def all(cls) -> "Uniform":
+        return cls(None)
+
+    def mask(self, n_actions: int) -> int:
+        """the allowed set in a space of ``n_actions`` as a bit mask (bit a = action a)"""
+        if self.actions is None:
+            return (1 << n_actions) - 1
+        for a in self.actions:
+            if a >= n_actions:
+                raise ValueError(f"Uniform: action {a} is outside the type's {n_actions} actions")
+        return sum(1 << a for a in self.actions)
+
+    def spelling(self) -> str:
+        """the command line's form: ``all``, or the actions joined with ``+``"""
+        return "all" if self.actions is None else "+".join(str(a) for a in self.actions)
+
+
+def masked_first_argmax(noise: np.ndarray, allowed: int):
+    """Per row of ``noise`` (float32 [B, A]) the smallest a with bit a of ``allowed`` set that maximises
+    noise[b, a]; returns (int32 [B], float32 [B]: the gap between the row's two largest allowed noises,
+    inf where one action is allowed)."""
+    noise = np.asarray(noise, dtype=np.float32)
+    A = noise.shape[1]
+    live = np.array([bool((allowed >> a) & 1) for a in range(A)])
+    if not live.any() or allowed >> A:
+        raise ValueError(f"allowed {allowed:#x} must be a non-empty mask of bits < {A}")
+    score = np.where(live[None, :], noise, -np.inf).astype(np.float32)
+    top = score.max(axis=1, keepdims=True)
+    actions = np.where(score == top, np.arange(A)[None, :], A).min(axis=1).astype(np.int32)
+    if live.sum() < 2:
+        return actions, np.full(noise.shape[0], np.inf, dtype=np.float32)
+    two = np.sort(score, axis=1)[:, -2:]
+    return actions, (two[:, 1] - two[:, 0]).astype(np.float32)
+
+
+def _check_draw(n_actors: int, n_actions: int, allowed: int) -> None:
+    if n_actors < 1:
+        raise ValueError("n_actors must be >= 1")
+    if not 1 <= n_actions <= MAX_DRAW_ACTIONS:
+        raise ValueError(f"n_actions must be 1..{MAX_DRAW_ACTIONS}, got {n_actions}")
+    if allowed <= 0 or allowed >> n_actions:
+        raise ValueError(f"allowed {allowed:#x} must be a non-empty mask of bits < {n_actions}")
+
+
+def draw_actions_reference(key, n_actors: int, n_actions: int, allowed: int):
+    """The draw of a uniform baseline policy, in numpy: actor b takes the smallest a with bit a of
+    ``allowed`` set that maximises g[b, a], g = jax.random.gumbel(key, (n_actors, n_actions)) under the
+    partitionable threefry in float32 (``train.policy.gumbel_noise``: the word of counter
+    (0, b n_actions + a)), which is jax.random.categorical on logits 0 on the allowed actions and -inf
+    elsewhere.  A mask of one bit draws nothing.  Returns (actions int32 [n_actors], gaps float32
+    [n_actors]): a row's gap is the distance between its two largest allowed noises; a device's float32
+    logarithm may round a last place differently, so tests hold only rows with a clear gap."""
+    from .train.policy import gumbel_noise
+    _check_draw(n_actors, n_actions, allowed)
+    if allowed & (allowed - 1) == 0:
+        return (np.full(n_actors, allowed.bit_length() - 1, dtype=np.int32),
+                np.full(n_actors, np.inf, dtype=np.float32))
+    return masked_first_argmax(gumbel_noise(key, n_actors, n_actions).numpy(), allowed)
+
+
+def _draw_launch(n_actors: int, n_actions: int, allowed: int, key: torch.Tensor, out: torch.Tensor) -> None:
+    """hftlob_draw_actions on checked device tensors (key [2], out int32 [n_actors] in any shape)"""
+    dev = out.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().hftlob_draw_actions(n_actors, n_actions, allowed, _lib.ptr(key), _lib.ptr(out),
+                                                  _lib.stream_ptr(device=dev)))
+
+
+def draw_actions(key: torch.Tensor, n_actors: int, n_actions: int, allowed: int,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`draw_actions_reference`'s actions as one launch of hftlob_draw_actions
+    (csrc/draw_actions.hip) on torch's current stream.  key: uint32 / int32 [2] on a GPU (there is no
+    other path); out: a contiguous int32 [n_actors] tensor on that device to fill, None allocates one.
+    Nothing else is allocated and nothing synchronises."""
+    _check_draw(n_actors, n_actions, allowed)
+    if not isinstance(key, torch.Tensor) or key.dtype not in (torch.int32, torch.uint32) or key.numel() != 2 \
+            or not key.is_contiguous():
+        raise ValueError("key must be a contiguous uint32/int32 tensor of two words")
+    if key.device.type != "cuda":
+        raise ValueError(f"draw_actions needs its key on a GPU device, got {key.device}")
+    if out is None:
+        out = torch.empty(n_actors, dtype=torch.int32, device=key.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.numel() != n_actors
+          or out.device != key.device or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous int32 [{n_actors}] tensor on {key.device}")
+    _draw_launch(n_actors, n_actions, allowed, key, out)
+    return out
+
+
+def draw_masks(env, entries: Sequence, fixed_too: bool = False) -> List[Optional[int]]:
+    """The allowed masks of checked policy entries (:func:`policy_entries`) on ``env``, one per agent
+    type: a :class:`Uniform`'s set in the type's space and None for the others, or with ``fixed_too``
+    (every type goes through the draw: :func:`evaluate_baseline`) a fixed action's one bit as well.
+    A type with a mask needs a Discrete space of at most 32 actions, and a :class:`Uniform` the env's
+    partitionable keys.  Host-only: nothing of the device is touched."""
+    masks: List[Optional[int]] = []
+    for t, (p, wd, sp) in enumerate(zip(entries, env.action_widths, env.action_spaces)):
+        if isinstance(p, torch.nn.Module) or (isinstance(p, int) and not fixed_too):
+            masks.append(None)
+            continue
+        if wd != 1 or not isinstance(sp.n, int):
+            raise ValueError(f"agent type {t}: a drawn baseline needs a Discrete action space, the type's is "
+                             f"MultiDiscrete ({wd} words per agent)")
+        if sp.n > MAX_DRAW_ACTIONS:
+            raise ValueError(f"agent type {t}: a drawn baseline covers at most {MAX_DRAW_ACTIONS} actions, the "
+                             f"type has {sp.n}")
+        if isinstance(p, Uniform):
+            try:
+                masks.append(p.mask(sp.n))
+            except ValueError as e:
+                raise ValueError(f"agent type {t}: {e}") from None
+        else:
+            if not 0 <= p < sp.n:
+                raise ValueError(f"agent type {t}: action {p} is outside the type's {sp.n} actions")
+            masks.append(1 << p)
+    if any(m is not None for m in masks) and not bool(env.cfg_c.prng_partitionable):
+        raise ValueError("a drawn baseline is built for the partitionable threefry only: the env has "
+                         "prng_partitionable off")
+    return masks
+
+
 def fixed_action_row(env, fixed_actions: Sequence) -> torch.Tensor:
     """FIXED_ACTIONS (one entry per agent type: an int, or a list of one int as the reference's
     configs write it) -> the int32 [action_words] row of ``rollout_eval(fixed=True)``: every agent
@@ -249,9 +416,7 @@ def fixed_action_row(env, fixed_actions: Sequence) -> torch.Tensor:
     for t, (a, n, wd) in enumerate(zip(fixed_actions, counts, env.action_widths)):
         if isinstance(a, (list, tuple)):
             if len(a) != 1:
-                raise NotImplementedError(
-                    f"agent type {t}: {len(a)} fixed actions; the reference draws one of them uniformly per step "
-                    "(JAX's categorical), which is not implemented: give one action per agent type")
+                raise _several_fixed_actions(t, len(a))
             a = a[0]
         row += [int(a)] * (n * wd)
     return torch.tensor(row, dtype=torch.int32, device=env.device)
@@ -305,27 +470,59 @@ def evaluate_fixed_actions(env, fixed_actions: Sequence, n_envs: int, n_steps: i
     return EvalStats(stats, env.layout)
 
 
+def evaluate_baseline(env, entries: Sequence, n_envs: int, n_steps: int, seed: int, chunk: int = 256) -> EvalStats:
+    """:func:`evaluate_fixed_actions` for baselines that draw: ``entries`` holds one int, list of one
+    int or :class:`Uniform` per agent type, in any mix, and one ``rollout_eval_drawn`` launch per
+    chunk draws every type's actions inside the env launch (a fixed action is a mask of one bit, which
+    draws nothing).  The reset and step keys are that function's chain unchanged; type i's draw key at
+    a step is ``split(act, n_types)[i]`` of the key the chain leaves unused (:func:`_key_chain`), what
+    :func:`evaluate_policy` hands the type, so the two give the same stats for the same entries.  Every
+    type needs a Discrete space of at most 32 actions, and a :class:`Uniform` partitionable keys."""
+    from .env import split_keys
+    if n_envs < 1 or n_steps < 1 or chunk < 1:
+        raise ValueError("n_envs, n_steps and chunk must be >= 1")
+    n_types = len(env.multi_agent_config.number_of_agents_per_type)
+    pols = policy_entries(entries, n_types)
+    for t, p in enumerate(pols):
+        if isinstance(p, torch.nn.Module):
+            raise TypeError(f"agent type {t}: evaluate_baseline takes fixed actions and Uniform entries; a network "
+                            "goes through evaluate_policy")
+    allowed = draw_masks(env, pols, fixed_too=True)
+    part = bool(env.cfg_c.prng_partitionable)
+    params = env.default_params
+    rng = torch.tensor([[0, int(seed) & 0xFFFFFFFF]], dtype=torch.int64).to(torch.int32).to(env.device)
+    pair = split_keys(rng, 2, part)
+    rng = pair[:, 0].contiguous()
+    _, state = env.reset(split_keys(pair[:, 1].contiguous(), n_envs, part)[0], params)
+    stats = None
+    for t0 in range(0, n_steps, chunk):
+        rng, sub, act = _key_chain(rng, min(chunk, n_steps - t0), part)
+        keys = split_keys(torch.cat(sub).contiguous(), n_envs, part)                      # [T, E, 2]
+        draw_keys = split_keys(torch.cat(act).contiguous(), n_types, part)                # [T, n_types, 2]
+        stats = env.rollout_eval_drawn(keys, state, draw_keys, allowed, params, stats=stats)[-1]
+    return EvalStats(stats, env.layout)
+
+
 def _fixed_action(t: int, a) -> int:
     """one type's fixed action as :func:`fixed_action_row` reads it: an int, or a list of one int"""
     if isinstance(a, (list, tuple)):
         if len(a) != 1:
-            raise NotImplementedError(
-                f"agent type {t}: {len(a)} fixed actions; the reference draws one of them uniformly per step "
-                "(JAX's categorical), which is not implemented: give one action per agent type")
+            raise _several_fixed_actions(t, len(a))
         a = a[0]
     if isinstance(a, bool) or not isinstance(a, int):
-        raise TypeError(f"agent type {t}: a policy entry must be an ActorCriticRNN, an int or a list of one int, "
-                        f"got {type(a).__name__}")
+        raise TypeError(f"agent type {t}: a policy entry must be an ActorCriticRNN, a Uniform, an int or a list of "
+                        f"one int, got {type(a).__name__}")
     return a
 
 
 def policy_entries(nets: Sequence, n_types: int) -> list:
     """The entries of :func:`evaluate_policy`'s ``nets`` checked, one per agent type: a network (any
-    ``torch.nn.Module``; an ``ActorCriticRNN`` is what runs) stays, a fixed action (an int, or a list
-    of one int as the reference's FIXED_ACTIONS writes it) becomes its int.  Host-only."""
+    ``torch.nn.Module``; an ``ActorCriticRNN`` is what runs) and a :class:`Uniform` stay, a fixed
+    action (an int, or a list of one int as the reference's FIXED_ACTIONS writes it) becomes its int.
+    Host-only."""
     if len(nets) != n_types:
         raise ValueError(f"nets must hold one network or fixed action per agent type ({n_types}), got {len(nets)}")
-    return [p if isinstance(p, torch.nn.Module) else _fixed_action(t, p) for t, p in enumerate(nets)]
+    return [p if isinstance(p, (torch.nn.Module, Uniform)) else _fixed_action(t, p) for t, p in enumerate(nets)]
 
 
 def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: bool = True,
@@ -342,7 +539,10 @@ def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: boo
     sample per head), followed by ``env.step`` and one :func:`tally_steps` launch over the env's own
     output buffers (rewards, raw info words, global dones): nothing is copied or kept per step.  The
     carries start at zero and are reset by each actor's done.  ``chunk`` sizes the key generation
-    only.  The env must be built with ``return_info=True``."""
+    only.  The env must be built with ``return_info=True``.
+    An entry may also be a :class:`Uniform`: the type (a Discrete space of at most 32 actions) has no
+    carry either, and its step is one :func:`draw_actions` launch under the type's policy key of the
+    step, the key a learned type would sample with; learned and fixed types are as without it."""
     from .env import split_keys
     from .train.policy import GREEDY, SAMPLE, policy_step_net
     if n_envs < 1 or n_steps < 1 or chunk < 1:
@@ -351,7 +551,9 @@ def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: boo
         raise ValueError("evaluate_policy reduces the steps' info words: build the env with return_info=True")
     counts = list(env.multi_agent_config.number_of_agents_per_type)
     pols = policy_entries(nets, len(counts))
-    learned = [i for i, p in enumerate(pols) if not isinstance(p, int)]
+    learned = [i for i, p in enumerate(pols) if isinstance(p, torch.nn.Module)]
+    drawn = [i for i, p in enumerate(pols) if isinstance(p, Uniform)]
+    allowed = draw_masks(env, pols) if drawn else None
     part = bool(env.cfg_c.prng_partitionable)
     params, dev, E, L = env.default_params, env.device, n_envs, env.layout
     mode = GREEDY if greedy else SAMPLE
@@ -363,6 +565,8 @@ def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: boo
     # a fixed type's action words, built once: [E, n_t * width]
     actions = [torch.full((E, n * wd), p, dtype=torch.int32, device=dev) if isinstance(p, int) else None
                for p, n, wd in zip(pols, counts, env.action_widths)]
+    for i in drawn:   # a drawn type's action words [E, n_t], refilled by its draw at every step
+        actions[i] = torch.empty((E, counts[i]), dtype=torch.int32, device=dev)
     obs = {i: obs[i].reshape(n_act[i], -1).contiguous() for i in learned}
     done = {i: torch.zeros(n_act[i], dtype=torch.bool, device=dev) for i in learned}
     h = {i: torch.zeros(n_act[i], pols[i].hidden, device=dev) for i in learned}
@@ -378,6 +582,8 @@ def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: boo
             for i in learned:
                 a = policy_step_net(pols[i], obs[i], done[i], h[i], mode, key=pol[t, i] if mode == SAMPLE else None)[1]
                 actions[i] = a.view(E, counts[i], *a.shape[1:])   # [E, n_t], or [E, n_t, K] of a MultiDiscrete type
+            for i in drawn:
+                _draw_launch(n_act[i], env.action_spaces[i].n, allowed[i], pol[t, i], actions[i])
             o, state, _, d, _ = env.step(keys[t], state, actions, params)
             # the step's raw outputs where the env launch wrote them: [E, A], [E, info_words], [E]
             _tally_launch(env.last_rewards.view(1, E, A), env.last_info_words.view(1, E, L.info_words),
@@ -420,18 +626,43 @@ def evaluate_combinations(env, nets, fixed_actions: Sequence, n_envs: int, n_ste
             for desc in combination_names(n)}
 
 
+def parse_entries(text: str) -> list:
+    """The command line's baseline entries, one per agent type, comma-separated: an int (a fixed
+    action), a ``+``-joined set (``1+2+3``: :class:`Uniform` over it) or ``all`` (``Uniform.all()``)."""
+    out = []
+    for item in text.split(","):
+        item = item.strip()
+        if item == "all":
+            out.append(Uniform.all())
+        elif "+" in item:
+            out.append(Uniform([int(x) for x in item.split("+")]))
+        else:
+            out.append(int(item))
+    return out
+
+
+def entry_spelling(p):
+    """a baseline entry as :func:`parse_entries` reads it (an int stays an int)"""
+    return p.spelling() if isinstance(p, Uniform) else p
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m hftlob.evaluate", description=__doc__.split("\n\n")[0])
     ap.add_argument("--env-config", required=True, help="a built-in config name, or the path of a config .json")
     what = ap.add_mutually_exclusive_group(required=True)
     what.add_argument("--fixed-actions",
                       help="one action per agent type, comma-separated (the reference's FIXED_ACTIONS)")
+    what.add_argument("--uniform-actions", metavar="1+2+3,all",
+                      help="one entry per agent type, comma-separated: a '+'-joined set drawn uniformly at every step "
+                           "(the reference's FixedAction with several actions), a single action, or 'all' (its "
+                           "RandomPolicy)")
     what.add_argument("--checkpoint", metavar="PATH",
                       help="evaluate the policies of an IPPOTrainer checkpoint (python -m hftlob.train.ippo --save)")
     ap.add_argument("--sample", action="store_true",
                     help="with --checkpoint: sample the actions (jax.random.categorical) instead of the argmax")
     ap.add_argument("--baseline-actions", metavar="A,B",
-                    help="with --checkpoint: one fixed action per agent type for the types a mix runs as baseline")
+                    help="with --checkpoint: one fixed action per agent type for the types a mix runs as baseline "
+                         "(or a drawn entry, as --uniform-actions spells it)")
     ap.add_argument("--combinations", action="store_true",
                     help="with --baseline-actions: every learned / baseline mix per agent type (BB, BL, LB, LL)")
     ap.add_argument("--mix", metavar="LB",
@@ -468,9 +699,10 @@ def main(argv=None) -> int:
         env = MARLEnv(None, cfg, data=day, device=args.device, return_info=True, persistent_outputs=True)
         nets = load_policy(args.checkpoint, env, args.device)
         if args.baseline_actions:
-            base = [int(x) for x in args.baseline_actions.split(",")]
+            base = parse_entries(args.baseline_actions)
             out = {"env_config": args.env_config, "checkpoint": args.checkpoint, "sample": bool(args.sample),
-                   "baseline_actions": base, "envs": args.envs, "steps": args.steps, "seed": args.seed}
+                   "baseline_actions": [entry_spelling(p) for p in base], "envs": args.envs, "steps": args.steps,
+                   "seed": args.seed}
             if args.combinations:
                 evs = evaluate_combinations(env, nets, base, args.envs, args.steps, args.seed, greedy=not args.sample)
             else:
@@ -487,6 +719,14 @@ def main(argv=None) -> int:
         print(json.dumps(out))
         return 0
     env = MARLEnv(None, cfg, data=day, device=args.device, return_info=False, persistent_outputs=True)
+    if args.uniform_actions:
+        entries = parse_entries(args.uniform_actions)
+        ev = evaluate_baseline(env, entries, args.envs, args.steps, args.seed, args.chunk or 256)
+        out = {"env_config": args.env_config, "uniform_actions": [entry_spelling(p) for p in entries],
+               "envs": args.envs, "steps": args.steps, "seed": args.seed}
+        out.update(ev.summary())
+        print(json.dumps(out))
+        return 0
     actions = [int(x) for x in args.fixed_actions.split(",")]
     ev = evaluate_fixed_actions(env, actions, args.envs, args.steps, args.seed, args.chunk or 256)
     out = {"env_config": args.env_config, "fixed_actions": actions, "envs": args.envs, "steps": args.steps,
