@@ -36,6 +36,8 @@
  *   hftlob_gru_scan_fwd / hftlob_gru_scan_bwd <- jaxrl/MARL/ippo_rnn_JAXMARL.py:53-78 ScannedRNN
  *                           (the nn.scan of a GRUCell whose carry is reset where done is set) and
  *                           its gradient through time, over a whole [T, B] sequence batch.
+ *   hftlob_gru_scan_fwd_grouped / hftlob_gru_scan_bwd_grouped <- the same scans of several independent
+ *                           nets (IPPO's one net per agent type) as one launch.
  *   hftlob_policy_step   <- jaxrl/MARL/ippo_rnn_JAXMARL.py:53-78, 183-256: one ActorCriticRNN step
  *                           (embedding, GRU cell, critic and actor heads) with the rollout's
  *                           pi.sample / log_prob (:590-600), for a batch of actors.
@@ -579,6 +581,40 @@ int hftlob_gru_scan_fwd(int T, int B, int H, const float* gi, const float* h0 /*
 int hftlob_gru_scan_bwd(int T, int B, int H, const float* d_hseq, const float* hseq, const float* gates,
                         const float* h0, const uint8_t* done, const float* w_hh, float* d_gi, float* d_gh_n,
                         float* d_h0, void* stream);
+
+/* The two scan operators over up to HFTLOB_GRU_MAX_GROUPS independent sequence batches ("groups": in
+ * IPPO, the minibatches of the agent types' nets) as one launch per direction.  The groups share T and
+ * H; each has its own B, arrays and weights (two groups may name the same w_hh / b_hh), with the
+ * layouts and meanings of the single-batch operators above.  groups is a host array that is read
+ * during the call only: the table travels by value in the kernel arguments, so the call makes no copy
+ * to the device and can be captured in a graph.  A workgroup owns one 16-row tile of one group; tiles
+ * never straddle groups, each group's tiles start at its row 0, and the grid is the sum of the groups'
+ * tile counts.  The per-tile arithmetic is that of hftlob_gru_scan_fwd / _bwd (one device function
+ * serves both), so every group's outputs equal bit for bit what the single-batch operator gives for
+ * that group alone, whatever the other groups and their order.
+ * HFTLOB_ESHAPE: n_groups outside 1..HFTLOB_GRU_MAX_GROUPS, T < 1, a group with B < 1, H not 64, 128
+ * or 256.  HFTLOB_ENULL: groups or any array of a group is NULL, except the forward's gates (NULL skips
+ * that group's gate stores and changes no bit of its hseq).  Rows past a group's B are neither read out
+ * of bounds nor written. */
+#define HFTLOB_GRU_MAX_GROUPS 8
+typedef struct {
+    int B;
+    const float *gi, *h0;
+    const uint8_t* done;
+    const float *w_hh, *b_hh;
+    float *hseq, *gates /* or NULL */;
+} hftlob_gru_fwd_group;
+typedef struct {
+    int B;
+    const float *d_hseq, *hseq, *gates, *h0;
+    const uint8_t* done;
+    const float* w_hh;
+    float *d_gi, *d_gh_n, *d_h0;
+} hftlob_gru_bwd_group;
+int hftlob_gru_scan_fwd_grouped(int T, int H, int n_groups, const hftlob_gru_fwd_group* groups /*[host]*/,
+                                void* stream);
+int hftlob_gru_scan_bwd_grouped(int T, int H, int n_groups, const hftlob_gru_bwd_group* groups /*[host]*/,
+                                void* stream);
 
 /* Fused recurrent policy step: one ActorCriticRNN step (jaxrl/MARL/ippo_rnn_JAXMARL.py:53-78 ScannedRNN's
  * cell, :183-256 SingleActionOutput and ActorCriticRNN) for a batch of B actors as one launch, float32.

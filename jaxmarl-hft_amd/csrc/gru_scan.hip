@@ -1,4 +1,6 @@
 // Fused GRU sequence scan for the IPPO learner (include/hftlob.h: hftlob_gru_scan_fwd / _bwd), gfx950.
+// hftlob_gru_scan_fwd_grouped / _bwd_grouped launch the tiles of several such scans (independent nets
+// that share T and H) at once; a tile's work is the same device function either way.
 //
 // The recurrent part of ScannedRNN (jaxrl/MARL/ippo_rnn_JAXMARL.py) is a dependent chain over
 // time whose batch rows are independent, so it is launched the way the env rollout is: once per
@@ -29,16 +31,17 @@
 
 namespace {
 
+// The forward scan of one tile: rows b0 .. b0 + 15 of a [T, B] sequence batch, all T steps.  The body of
+// both entry points (one batch, and the grouped launch whose workgroup has looked up its group first).
 template <int H, int CB>
-__global__ __launch_bounds__(64 * (H / 16 / CB)) void k_gru_scan_fwd(
-    int T, int B, const float* __restrict__ gi, const float* __restrict__ h0, const uint8_t* __restrict__ done,
-    const float* __restrict__ w_hh, const float* __restrict__ b_hh, float* __restrict__ hseq,
-    float* __restrict__ gates) {
+__device__ __forceinline__ void gru_fwd_tile(
+    int T, int B, int b0, const float* __restrict__ gi, const float* __restrict__ h0,
+    const uint8_t* __restrict__ done, const float* __restrict__ w_hh, const float* __restrict__ b_hh,
+    float* __restrict__ hseq, float* __restrict__ gates) {
     constexpr int NW = H / 16 / CB, NT = 64 * NW, S = H + 4, NCH = H / 32, PF = 2;  // chunks of 32 k
     static_assert(NCH % PF == 0 && (NCH & (NCH - 1)) == 0, "the k loop is unrolled by PF chunks and wraps by a mask");
     __shared__ __attribute__((aligned(16))) float hbuf[2][TILE * S];  // h_prev(t) of the tile, by t & 1
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, li = l & 15, q = l >> 4;
-    const int b0 = blockIdx.x * TILE;
 
     for (int i = tid; i < TILE * H; i += NT) {  // h_prev(0) = done[0] ? 0 : h0; rows past B are zero
         const int row = i / H, j = i % H, b = b0 + row;
@@ -148,9 +151,10 @@ __global__ __launch_bounds__(64 * (H / 16 / CB)) void k_gru_scan_fwd(
     }
 }
 
+// The backward scan of one tile, as gru_fwd_tile is the forward's
 template <int H>
-__global__ __launch_bounds__(64 * (H / 64)) void k_gru_scan_bwd(
-    int T, int B, const float* __restrict__ d_hseq, const float* __restrict__ hseq,
+__device__ __forceinline__ void gru_bwd_tile(
+    int T, int B, int b0, const float* __restrict__ d_hseq, const float* __restrict__ hseq,
     const float* __restrict__ gates, const float* __restrict__ h0, const uint8_t* __restrict__ done,
     const float* __restrict__ w_hh, float* __restrict__ d_gi, float* __restrict__ d_gh_n,
     float* __restrict__ d_h0) {
@@ -158,7 +162,6 @@ __global__ __launch_bounds__(64 * (H / 64)) void k_gru_scan_bwd(
     static_assert(NCH % PF == 0, "the k loop is unrolled by PF chunks");
     __shared__ __attribute__((aligned(16))) float dgh[TILE * S];  // d_gh[t] of the tile: (dr, dz, dn r)
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, li = l & 15, q = l >> 4;
-    const int b0 = blockIdx.x * TILE;
     const int j0 = w * 64 + 4 * li;  // the lane's hidden indices j0 .. j0 + 3: column li of blocks 0 .. 3
     const float* wp = w_hh + (size_t)(4 * q) * H + j0;  // the lane's B operand: W_hh[4 q + ...][j0 ..]
 
@@ -243,9 +246,103 @@ __global__ __launch_bounds__(64 * (H / 64)) void k_gru_scan_bwd(
     }
 }
 
+template <int H, int CB>
+__global__ __launch_bounds__(64 * (H / 16 / CB)) void k_gru_scan_fwd(
+    int T, int B, const float* __restrict__ gi, const float* __restrict__ h0, const uint8_t* __restrict__ done,
+    const float* __restrict__ w_hh, const float* __restrict__ b_hh, float* __restrict__ hseq,
+    float* __restrict__ gates) {
+    gru_fwd_tile<H, CB>(T, B, blockIdx.x * TILE, gi, h0, done, w_hh, b_hh, hseq, gates);
+}
+
+template <int H>
+__global__ __launch_bounds__(64 * (H / 64)) void k_gru_scan_bwd(
+    int T, int B, const float* __restrict__ d_hseq, const float* __restrict__ hseq,
+    const float* __restrict__ gates, const float* __restrict__ h0, const uint8_t* __restrict__ done,
+    const float* __restrict__ w_hh, float* __restrict__ d_gi, float* __restrict__ d_gh_n,
+    float* __restrict__ d_h0) {
+    gru_bwd_tile<H>(T, B, blockIdx.x * TILE, d_hseq, hseq, gates, h0, done, w_hh, d_gi, d_gh_n, d_h0);
+}
+
+// The grouped launches (hftlob_gru_scan_fwd_grouped / _bwd_grouped): the groups by value in the kernel
+// arguments, as optim_step.hip's tensor table travels, so that the call needs no copy to the device and
+// can be captured in a graph.  first[g] is group g's first tile, first[MAXG] the grid; the unused entries
+// repeat group 0 and have no tiles.  A workgroup finds its group from blockIdx once, before the t loop:
+// the index is wave-uniform, so the group's B and pointers are scalar loads from the kernarg segment
+// and live in SGPRs as the arguments of the single-batch kernels do.
+constexpr int MAXG = HFTLOB_GRU_MAX_GROUPS;
+
+template <class G>
+struct GroupTable {
+    G g[MAXG];
+    int first[MAXG + 1];
+};
+
+template <class G>
+__device__ __forceinline__ int find_group(const GroupTable<G>& tb, int tile) {
+    int g = 0;
+    while (tile >= tb.first[g + 1]) ++g;  // (the grid is first[MAXG] workgroups: g stays below MAXG)
+    return g;
+}
+
+template <int H, int CB>
+__global__ __launch_bounds__(64 * (H / 16 / CB)) void k_gru_scan_fwd_grouped(
+    int T, const GroupTable<hftlob_gru_fwd_group> tb) {
+    const int g = find_group(tb, blockIdx.x);
+    const hftlob_gru_fwd_group& x = tb.g[g];
+    gru_fwd_tile<H, CB>(T, x.B, (blockIdx.x - tb.first[g]) * TILE, x.gi, x.h0, x.done, x.w_hh, x.b_hh, x.hseq,
+                        x.gates);
+}
+
+template <int H>
+__global__ __launch_bounds__(64 * (H / 64)) void k_gru_scan_bwd_grouped(
+    int T, const GroupTable<hftlob_gru_bwd_group> tb) {
+    const int g = find_group(tb, blockIdx.x);
+    const hftlob_gru_bwd_group& x = tb.g[g];
+    gru_bwd_tile<H>(T, x.B, (blockIdx.x - tb.first[g]) * TILE, x.d_hseq, x.hseq, x.gates, x.h0, x.done, x.w_hh,
+                    x.d_gi, x.d_gh_n, x.d_h0);
+}
+
+int check_TH(int T, int H) {
+    if (T < 1) return hftlob_fail(HFTLOB_ESHAPE, "gru_scan: T and B must be >= 1");
+    if (H != 64 && H != 128 && H != 256) return hftlob_fail(HFTLOB_ESHAPE, "gru_scan: H must be 64, 128 or 256");
+    return HFTLOB_OK;
+}
+
 int check_shape(int T, int B, int H) {
     if (T < 1 || B < 1) return hftlob_fail(HFTLOB_ESHAPE, "gru_scan: T and B must be >= 1");
-    if (H != 64 && H != 128 && H != 256) return hftlob_fail(HFTLOB_ESHAPE, "gru_scan: H must be 64, 128 or 256");
+    return check_TH(T, H);
+}
+
+bool has_null(const hftlob_gru_fwd_group& x) {  // (gates may be NULL)
+    return !x.gi || !x.h0 || !x.done || !x.w_hh || !x.b_hh || !x.hseq;
+}
+
+bool has_null(const hftlob_gru_bwd_group& x) {
+    return !x.d_hseq || !x.hseq || !x.gates || !x.h0 || !x.done || !x.w_hh || !x.d_gi || !x.d_gh_n || !x.d_h0;
+}
+
+// the checks of a grouped call and its table; *grid receives the number of tiles
+template <class G>
+int make_table(int T, int H, int n_groups, const G* groups, GroupTable<G>* tb, unsigned* grid) {
+    if (n_groups < 1 || n_groups > MAXG) return hftlob_fail(HFTLOB_ESHAPE, "gru_scan grouped: n_groups must be in 1..8");
+    if (const int rc = check_TH(T, H)) return rc;
+    if (!groups) return hftlob_fail(HFTLOB_ENULL, "gru_scan grouped: groups is NULL");
+    long long tiles = 0;
+    for (int g = 0; g < MAXG; ++g) {
+        tb->first[g] = (int)tiles;
+        if (g >= n_groups) {
+            tb->g[g] = groups[0];
+            continue;
+        }
+        const G& x = groups[g];
+        if (x.B < 1) return hftlob_fail(HFTLOB_ESHAPE, "gru_scan grouped: a group's B must be >= 1");
+        if (has_null(x)) return hftlob_fail(HFTLOB_ENULL, "gru_scan grouped: null array in a group");
+        tb->g[g] = x;
+        tiles += (x.B + TILE - 1) / TILE;
+        if (tiles > INT32_MAX) return hftlob_fail(HFTLOB_ESHAPE, "gru_scan grouped: more than 2^31 - 1 tiles");
+    }
+    tb->first[MAXG] = (int)tiles;
+    *grid = (unsigned)tiles;
     return HFTLOB_OK;
 }
 
@@ -276,6 +373,30 @@ int hftlob_gru_scan_bwd(int T, int B, int H, const float* d_hseq, const float* h
     if (H == 64) k_gru_scan_bwd<64><<<grid, 64, 0, s>>>(T, B, d_hseq, hseq, gates, h0, done, w_hh, d_gi, d_gh_n, d_h0);
     else if (H == 128) k_gru_scan_bwd<128><<<grid, 128, 0, s>>>(T, B, d_hseq, hseq, gates, h0, done, w_hh, d_gi, d_gh_n, d_h0);
     else k_gru_scan_bwd<256><<<grid, 256, 0, s>>>(T, B, d_hseq, hseq, gates, h0, done, w_hh, d_gi, d_gh_n, d_h0);
+    return launch_status();
+}
+
+int hftlob_gru_scan_fwd_grouped(int T, int H, int n_groups, const hftlob_gru_fwd_group* groups, void* stream) {
+    GroupTable<hftlob_gru_fwd_group> tb;
+    unsigned tiles = 0;
+    if (const int rc = make_table(T, H, n_groups, groups, &tb, &tiles)) return rc;
+    const dim3 grid(tiles);
+    hipStream_t s = (hipStream_t)stream;
+    if (H == 64) k_gru_scan_fwd_grouped<64, 1><<<grid, 256, 0, s>>>(T, tb);
+    else if (H == 128) k_gru_scan_fwd_grouped<128, 1><<<grid, 512, 0, s>>>(T, tb);
+    else k_gru_scan_fwd_grouped<256, 2><<<grid, 512, 0, s>>>(T, tb);
+    return launch_status();
+}
+
+int hftlob_gru_scan_bwd_grouped(int T, int H, int n_groups, const hftlob_gru_bwd_group* groups, void* stream) {
+    GroupTable<hftlob_gru_bwd_group> tb;
+    unsigned tiles = 0;
+    if (const int rc = make_table(T, H, n_groups, groups, &tb, &tiles)) return rc;
+    const dim3 grid(tiles);
+    hipStream_t s = (hipStream_t)stream;
+    if (H == 64) k_gru_scan_bwd_grouped<64><<<grid, 64, 0, s>>>(T, tb);
+    else if (H == 128) k_gru_scan_bwd_grouped<128><<<grid, 128, 0, s>>>(T, tb);
+    else k_gru_scan_bwd_grouped<256><<<grid, 256, 0, s>>>(T, tb);
     return launch_status();
 }
 

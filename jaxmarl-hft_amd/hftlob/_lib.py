@@ -24,6 +24,17 @@ class AdamTensor(C.Structure):
                 ("n", C.c_longlong)]
 
 
+class GruFwdGroup(C.Structure):
+    """hftlob_gru_fwd_group (include/hftlob.h): one group of hftlob_gru_scan_fwd_grouped."""
+    _fields_ = [("B", C.c_int)] + [(k, C.c_void_p) for k in ("gi", "h0", "done", "w_hh", "b_hh", "hseq", "gates")]
+
+
+class GruBwdGroup(C.Structure):
+    """hftlob_gru_bwd_group (include/hftlob.h): one group of hftlob_gru_scan_bwd_grouped."""
+    _fields_ = [("B", C.c_int)] + [(k, C.c_void_p) for k in ("d_hseq", "hseq", "gates", "h0", "done", "w_hh", "d_gi",
+                                                             "d_gh_n", "d_h0")]
+
+
 class PolicyWeights(C.Structure):
     """hftlob_policy_weights (include/hftlob.h): device pointers of one ActorCriticRNN's parameters."""
     _fields_ = [(n, C.c_void_p) for n in ("w_embed", "b_embed", "w_ih", "b_ih", "w_hh", "b_hh", "w_c1", "b_c1",
@@ -40,6 +51,7 @@ EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob
            "hftlob_draw_actions", "hftlob_env_rollout_eval_drawn",
            "hftlob_env_lds_bytes", "hftlob_env_launch_info", "hftlob_env_baked_id", "hftlob_set_baked",
            "hftlob_sample_actions", "hftlob_split_keys", "hftlob_gru_scan_fwd", "hftlob_gru_scan_bwd",
+           "hftlob_gru_scan_fwd_grouped", "hftlob_gru_scan_bwd_grouped",
            "hftlob_policy_step", "hftlob_policy_step_multi", "hftlob_gae", "hftlob_ppo_loss",
            "hftlob_adam_clip")
 
@@ -106,6 +118,10 @@ def lib() -> C.CDLL:
     L.hftlob_gru_scan_fwd.restype = i32
     L.hftlob_gru_scan_bwd.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.hftlob_gru_scan_bwd.restype = i32
+    L.hftlob_gru_scan_fwd_grouped.argtypes = [i32, i32, i32, C.POINTER(GruFwdGroup), vp]
+    L.hftlob_gru_scan_fwd_grouped.restype = i32
+    L.hftlob_gru_scan_bwd_grouped.argtypes = [i32, i32, i32, C.POINTER(GruBwdGroup), vp]
+    L.hftlob_gru_scan_bwd_grouped.restype = i32
     L.hftlob_policy_step.argtypes = [i32, i32, i32, i32, i32, C.POINTER(PolicyWeights), vp, vp, vp, vp, i32, vp,
                                      vp, vp, vp, vp, vp]
     L.hftlob_policy_step.restype = i32

@@ -1,6 +1,10 @@
 """The learner's GRU sequence scan (ScannedRNN, ippo_rnn_JAXMARL.py:53-78) as two engine
 operators and their autograd wrapper.
 
+``gru_scan_grouped`` is the same scan for several independent nets at once (IPPO's one net per agent
+type): ``hftlob_gru_scan_fwd_grouped`` / ``_bwd_grouped``, one launch per direction for all the groups,
+every group's results bit for bit those of ``gru_scan`` on that group alone.
+
 ``gru_scan_reference`` / ``gru_scan_backward_reference`` restate ``hftlob_gru_scan_fwd`` /
 ``hftlob_gru_scan_bwd`` (include/hftlob.h) in torch, in whatever float type they are given: they
 are the spec of the kernels and what the tests compare against.  ``gru_scan`` is the fused path:
@@ -18,11 +22,17 @@ import torch
 from .. import _lib
 
 SUPPORTED_HIDDEN = (64, 128, 256)   # the kernels' template instantiations (csrc/gru_scan.hip)
+MAX_GROUPS = 8                      # HFTLOB_GRU_MAX_GROUPS: sequence batches in one grouped launch
 
 
 def gru_scan_supported(hidden: int) -> bool:
     """Whether the fused scan has a kernel for this hidden size (no GPU needed to ask)."""
     return int(hidden) in SUPPORTED_HIDDEN
+
+
+def gru_scan_grouped_supported(hidden: int, n_groups: int) -> bool:
+    """Whether the grouped scan takes this many groups of this hidden size (no GPU needed to ask)."""
+    return gru_scan_supported(hidden) and 1 <= int(n_groups) <= MAX_GROUPS
 
 
 def _h_prev(hseq, h0, done):
@@ -144,3 +154,124 @@ class GRUScan(torch.autograd.Function):
 def gru_scan(gi, h0, done, w_hh, b_hh):
     """The fused scan: hseq [T, B, H] (float32, on the device of ``gi``)."""
     return GRUScan.apply(gi, h0, done, w_hh, b_hh)
+
+
+def _check_groups(what: str, shapes) -> tuple:
+    """(T, H) of a grouped call from its groups' (T, B, H); raises before anything is launched."""
+    shapes = list(shapes)
+    if not 1 <= len(shapes) <= MAX_GROUPS:
+        raise ValueError(f"{what}: needs 1..{MAX_GROUPS} groups, got {len(shapes)}")
+    T, _, H = shapes[0]
+    for g, (t, _, h) in enumerate(shapes):
+        if (t, h) != (T, H):
+            raise ValueError(f"{what}: every group must have the same T and H, group 0 has ({T}, {H}), "
+                             f"group {g} ({t}, {h})")
+    return T, H
+
+
+def scan_forward_grouped(groups, save_gates=True):
+    """hftlob_gru_scan_fwd_grouped on device tensors: ``groups`` is a sequence of (gi, h0, done, w_hh, b_hh),
+    ``save_gates`` a bool or one per group; returns a list of (hseq, gates or None), one launch for all."""
+    groups = [tuple(g) for g in groups]
+    save = list(save_gates) if isinstance(save_gates, (list, tuple)) else [bool(save_gates)] * len(groups)
+    if len(save) != len(groups):
+        raise ValueError(f"gru_scan grouped: {len(groups)} groups, {len(save)} save_gates")
+    for g in groups:
+        if len(g) != 5 or g[0].dim() != 3 or g[0].shape[2] % 3:
+            raise ValueError("gru_scan grouped: a group is (gi [T, B, 3H], h0, done, w_hh, b_hh)")
+    T, H = _check_groups("gru_scan grouped", [(g[0].shape[0], g[0].shape[1], g[0].shape[2] // 3) for g in groups])
+    rows, keep, out = [], [], []
+    for k, (gi, h0, done, w_hh, b_hh) in enumerate(groups):
+        B = gi.shape[1]
+        gi, h0, w_hh, b_hh, done = _f32(gi), _f32(h0), _f32(w_hh), _f32(b_hh), _u8(done)
+        if h0.shape != (B, H) or done.shape != (T, B) or w_hh.shape != (3 * H, H) or b_hh.shape != (3 * H,):
+            raise ValueError(f"gru_scan grouped, group {k}: shapes gi {tuple(gi.shape)}, h0 {tuple(h0.shape)}, done "
+                             f"{tuple(done.shape)}, w_hh {tuple(w_hh.shape)}, b_hh {tuple(b_hh.shape)} do not agree")
+        ptrs = [_lib.ptr(x) for x in (gi, h0, done, w_hh, b_hh)]   # (a CPU tensor raises here)
+        hseq = torch.empty((T, B, H), dtype=torch.float32, device=gi.device)
+        gates = torch.empty((T, B, 4 * H), dtype=torch.float32, device=gi.device) if save[k] else None
+        rows.append(_lib.GruFwdGroup(B, *ptrs, _lib.ptr(hseq), _lib.ptr(gates)))
+        keep.append((gi, h0, done, w_hh, b_hh))   # (the converted copies live until the launch is made)
+        out.append((hseq, gates))
+    arr = (_lib.GruFwdGroup * len(rows))(*rows)
+    _lib.check(_lib.lib().hftlob_gru_scan_fwd_grouped(T, H, len(rows), arr, _lib.stream_ptr(device=out[0][0].device)))
+    return out
+
+
+def scan_backward_grouped(groups):
+    """hftlob_gru_scan_bwd_grouped on device tensors: ``groups`` is a sequence of (d_hseq, hseq, gates, h0,
+    done, w_hh); returns a list of (d_gi, d_gh_n, d_h0), one launch for all."""
+    groups = [tuple(g) for g in groups]
+    for g in groups:
+        if len(g) != 6 or g[1].dim() != 3:
+            raise ValueError("gru_scan grouped backward: a group is (d_hseq, hseq [T, B, H], gates, h0, done, w_hh)")
+    T, H = _check_groups("gru_scan grouped backward", [tuple(g[1].shape) for g in groups])
+    rows, keep, out = [], [], []
+    for k, (d_hseq, hseq, gates, h0, done, w_hh) in enumerate(groups):
+        B = hseq.shape[1]
+        d_hseq, hseq, gates, h0, w_hh, done = _f32(d_hseq), _f32(hseq), _f32(gates), _f32(h0), _f32(w_hh), _u8(done)
+        if d_hseq.shape != (T, B, H) or gates.shape != (T, B, 4 * H) or h0.shape != (B, H) or done.shape != (T, B) \
+                or w_hh.shape != (3 * H, H):
+            raise ValueError(f"gru_scan grouped backward, group {k}: shapes do not agree")
+        ptrs = [_lib.ptr(x) for x in (d_hseq, hseq, gates, h0, done, w_hh)]
+        d_gi = torch.empty((T, B, 3 * H), dtype=torch.float32, device=hseq.device)
+        d_gh_n = torch.empty((T, B, H), dtype=torch.float32, device=hseq.device)
+        d_h0 = torch.empty((B, H), dtype=torch.float32, device=hseq.device)
+        rows.append(_lib.GruBwdGroup(B, *ptrs, _lib.ptr(d_gi), _lib.ptr(d_gh_n), _lib.ptr(d_h0)))
+        keep.append((d_hseq, hseq, gates, h0, done, w_hh))
+        out.append((d_gi, d_gh_n, d_h0))
+    arr = (_lib.GruBwdGroup * len(rows))(*rows)
+    _lib.check(_lib.lib().hftlob_gru_scan_bwd_grouped(T, H, len(rows), arr, _lib.stream_ptr(device=out[0][0].device)))
+    return out
+
+
+class GRUScanGrouped(torch.autograd.Function):
+    """(hseq_0, ..) = gru_scan_grouped over n groups; the inputs are flattened as the n gi, the n h0, the n
+    done, the n w_hh and the n b_hh.  Every group is differentiable in its gi, h0, w_hh and b_hh."""
+
+    @staticmethod
+    def forward(ctx, n, *flat):
+        gis, h0s, dones, w_hhs, b_hhs = (flat[k * n:(k + 1) * n] for k in range(5))
+        # (needs_input_grad[0] is n's)
+        need = [any(ctx.needs_input_grad[1 + k * n + g] for k in (0, 1, 3, 4)) for g in range(n)]
+        out = scan_forward_grouped(list(zip(gis, h0s, dones, w_hhs, b_hhs)), save_gates=need)
+        ctx.n, ctx.need = n, need
+        saved = []
+        for g in range(n):
+            if need[g]:
+                saved += [out[g][0], out[g][1], _f32(h0s[g]), dones[g], _f32(w_hhs[g])]
+        ctx.save_for_backward(*saved)
+        return tuple(hseq for hseq, _ in out)
+
+    @staticmethod
+    def backward(ctx, *d_hseqs):
+        # (a group whose hseq received no gradient arrives as autograd's materialised zeros)
+        n, need, saved = ctx.n, ctx.need, ctx.saved_tensors
+        live = [g for g in range(n) if need[g]]
+        per = {g: saved[5 * i:5 * i + 5] for i, g in enumerate(live)}
+        grads = [None] * (5 * n)
+        if live:
+            # the stream is taken inside the call: autograd runs this under the forward's stream guard
+            res = scan_backward_grouped([(d_hseqs[g],) + tuple(per[g]) for g in live])
+            for g, (d_gi, d_gh_n, d_h0) in zip(live, res):
+                hseq, _, h0, done, _ = per[g]
+                grads[g], grads[n + g] = d_gi, d_h0
+                if ctx.needs_input_grad[1 + 3 * n + g] or ctx.needs_input_grad[1 + 4 * n + g]:
+                    grads[3 * n + g], grads[4 * n + g] = weight_grads(d_gi, d_gh_n, hseq, h0, done)
+        return (None, *grads)
+
+
+def gru_scan_grouped(gis, h0s, dones, w_hhs, b_hhs):
+    """The fused scans of several independent nets as one launch per direction: a tuple of hseq [T, B_g, H],
+    group g's equal bit for bit to ``gru_scan(gis[g], h0s[g], dones[g], w_hhs[g], b_hhs[g])``, and so are
+    its gradients (the weight and bias gradients are ``weight_grads`` per group)."""
+    lists = [list(x) for x in (gis, h0s, dones, w_hhs, b_hhs)]
+    n = len(lists[0])
+    if any(len(x) != n for x in lists):
+        raise ValueError(f"gru_scan_grouped: the five lists must have one entry per group, got "
+                         f"{[len(x) for x in lists]}")
+    for gi in lists[0]:
+        if gi.dim() != 3 or gi.shape[2] % 3:
+            raise ValueError("gru_scan_grouped: gi must be [T, B, 3H]")
+    _check_groups("gru_scan_grouped", [(gi.shape[0], gi.shape[1], gi.shape[2] // 3) for gi in lists[0]])
+    return GRUScanGrouped.apply(n, *(t for x in lists for t in x))

@@ -37,6 +37,10 @@ rollout reads torch's generator.  With ``FUSED_LOSS`` the update's GAE is one HI
 minibatch step's loss with its gradient three (``train.loss.gae``, ``train.loss.ppo_loss_fused``).
 With ``FUSED_OPT`` the minibatch step's clipping and Adam step are two HIP launches per agent type
 (``train.optim.adam_clip_step``) on capturable Adam's state, so the checkpoints do not change.
+With ``GROUPED_SCAN`` (on top of ``FUSED_GRU``) the agent types' minibatch steps run in lockstep as one
+joint step whose sequence scans are one HIP launch per direction for all the types
+(``train.gru.gru_scan_grouped``): the nets and their data are independent, so every parameter, optimiser
+state and metric is bit for bit what the per-type steps give.
 """
 from __future__ import annotations
 
@@ -50,7 +54,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..env import MARLEnv, split_keys
-from .gru import SUPPORTED_HIDDEN, gru_scan, gru_scan_supported
+from .gru import MAX_GROUPS, SUPPORTED_HIDDEN, gru_scan, gru_scan_grouped, gru_scan_supported
 from .loss import gae as gae_fused, ppo_loss_fused, ppo_loss_supported
 from .optim import MAX_TENSORS, adam_clip_step, adam_clip_supported, init_adam_state
 from .policy import MAX_ACTIONS, MAX_HEADS, MAX_OBS_DIM, SAMPLE, policy_step_multi_supported, policy_step_net
@@ -69,7 +73,8 @@ def default_config(**kw) -> Dict:
          "GAE_LAMBDA": [0.85, 0.9], "CLIP_EPS": 0.2, "ENT_COEF": [0.01, 0.01], "VF_COEF": [0.5, 0.5],
          "MAX_GRAD_NORM": [0.5, 0.5], "ANNEAL_LR": [True, True], "NUM_AGENTS_PER_TYPE": [1, 1], "SEED": 2,
          "CUDA_GRAPHS": True, "FUSED_GRU": False, "FUSED_POLICY": False, "FUSED_LOSS": False,
-         "FUSED_OPT": False, "CALC_EVAL": False, "NUM_STEPS_EVAL": None}   # NUM_STEPS_EVAL None: NUM_STEPS
+         "FUSED_OPT": False, "GROUPED_SCAN": False, "CALC_EVAL": False,
+         "NUM_STEPS_EVAL": None}   # NUM_STEPS_EVAL None: NUM_STEPS
     c.update(kw)
     return c
 
@@ -138,15 +143,38 @@ class ActorCriticRNN(nn.Module):
             hs.append(h)
         return torch.stack(hs)
 
+    def gi_all(self, obs: torch.Tensor) -> torch.Tensor:
+        """The input side of ``forward``: the embedding and the GRU's input projection over all T at once,
+        [T, B, 3H] in gate order (r, z, n)."""
+        return F.linear(F.relu(self.embed(obs)), self.gru.weight_ih, self.gru.bias_ih)
+
+    def head_outputs(self, hseq: torch.Tensor):
+        """The heads of ``forward`` on the scan's hseq [T, B, H]: logits [T, B, A], values [T, B]."""
+        return self.actor2(F.relu(self.actor1(hseq))), self.critic2(F.relu(self.critic1(hseq))).squeeze(-1)
+
     def forward(self, h0: torch.Tensor, obs: torch.Tensor, dones: torch.Tensor):
         """A sequence [T, B, ...] from carry h0 (the ScannedRNN scan): logits [T, B, A], values [T, B].
         The same cell as ``step``; the input-side GEMMs (embedding, the GRU's input
         projection, both heads) run once over all T, only h @ W_hh stays in the scan: the loop
         of ``scan_loop``, or with ``fused`` set one HIP launch forward and one backward."""
-        gi_all = F.linear(F.relu(self.embed(obs)), self.gru.weight_ih, self.gru.bias_ih)  # [T, B, 3H], (r, z, n)
         scan = gru_scan if self.fused else self.scan_loop
-        hseq = scan(gi_all, h0, dones, self.gru.weight_hh, self.gru.bias_hh)
-        return self.actor2(F.relu(self.actor1(hseq))), self.critic2(F.relu(self.critic1(hseq))).squeeze(-1)
+        hseq = scan(self.gi_all(obs), h0, dones, self.gru.weight_hh, self.gru.bias_hh)
+        return self.head_outputs(hseq)
+
+    @staticmethod
+    def forward_grouped(nets, h0s, obss, dones):
+        """``forward`` of several independent nets on their own sequences: a list of (logits, values), net
+        k's equal bit for bit to ``nets[k](h0s[k], obss[k], dones[k])``.  With every net ``fused`` the
+        scans are one HIP launch forward and one backward for all the nets (``gru_scan_grouped``; the
+        nets share T and the hidden size, each has its own B); otherwise each net runs its ``scan_loop``."""
+        gis = [net.gi_all(obs) for net, obs in zip(nets, obss)]
+        if all(net.fused for net in nets):
+            hseqs = gru_scan_grouped(gis, h0s, dones, [net.gru.weight_hh for net in nets],
+                                     [net.gru.bias_hh for net in nets])
+        else:
+            hseqs = [net.scan_loop(gi, h0, d, net.gru.weight_hh, net.gru.bias_hh)
+                     for net, gi, h0, d in zip(nets, gis, h0s, dones)]
+        return [net.head_outputs(hseq) for net, hseq in zip(nets, hseqs)]
 
 
 @dataclass
@@ -250,6 +278,17 @@ class IPPOTrainer:
         n_global = int(c["NUM_ENVS"])
         if n_global % world:
             raise ValueError(f"NUM_ENVS ({n_global}) must be a multiple of the world size ({world})")
+        # GROUPED_SCAN: the agent types' minibatch steps in lockstep, their scans one launch per direction
+        # (train.gru.gru_scan_grouped).  It follows FUSED_GRU's device rule: on the CPU the scans are the loops
+        self.grouped_scan = bool(c.get("GROUPED_SCAN", False))
+        if self.grouped_scan:
+            if not c.get("FUSED_GRU", False):
+                raise ValueError("GROUPED_SCAN needs FUSED_GRU")
+            if nt > MAX_GROUPS:
+                raise ValueError(f"GROUPED_SCAN needs <= {MAX_GROUPS} agent types, got {nt}")
+            if world > 1:
+                raise ValueError(f"GROUPED_SCAN is single-process (the gradient all-reduce is per agent type), "
+                                 f"got a world size of {world}")
         self.E, self.T = n_global // world, c["NUM_STEPS"]
         self.n_agents = list(env.multi_agent_config.number_of_agents_per_type)
         self.n_actors = [n * self.E for n in self.n_agents]
@@ -333,6 +372,7 @@ class IPPOTrainer:
             for opt in self.opts:
                 init_adam_state(opt)
         self._roll = None        # the captured rollout graph (False: not capturable, stays eager)
+        self._joint = {"warm": 0, "graph": None, "out": None}   # GROUPED_SCAN: the joint step's graph, as _st[i]'s
         self.opt_count = [0] * nt
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(c["SEED"] + 1000 * rank)
@@ -494,35 +534,124 @@ class IPPOTrainer:
         st["graph"].replay()
         return st["out"].clone()
 
+    def _joint_step(self) -> List[torch.Tensor]:
+        """GROUPED_SCAN: one PPO minibatch step of every agent type from the static inputs, the types'
+        scans grouped (``forward_grouped``); per type what ``_mb_step`` does (single process: no pmean)."""
+        c, T = self.c, self.T
+        idxs = [st["idx"] for st in self._st]
+        fw = ActorCriticRNN.forward_grouped(self.nets, [st["h0"][idx] for st, idx in zip(self._st, idxs)],
+                                            [b.obs[:, idx] for b, idx in zip(self.buf, idxs)],
+                                            [b.done[:, idx] for b, idx in zip(self.buf, idxs)])
+        loss_fn = ppo_loss_fused if self.fused_loss else ppo_loss_multi
+        outs = []
+        for i, (net, b, st, idx, (logits, values)) in enumerate(zip(self.nets, self.buf, self._st, idxs, fw)):
+            outs.append(loss_fn(logits, values, b.action[:, idx].view(T, -1, len(net.heads)), b.value[:, idx],
+                                b.log_prob[:, idx], st["adv"][:, idx], st["tgt"][:, idx], c["CLIP_EPS"], c["VF_COEF"][i],
+                                c["ENT_COEF"][i], net.heads))
+        # the list of totals, not their sum: the grouped scan's backward runs once, when every type's
+        # gradient of its hseq has arrived, and no type's gradient passes through an addition
+        torch.autograd.backward([out[0] for out in outs])
+        for i, (net, opt) in enumerate(zip(self.nets, self.opts)):
+            if self.fused_opt:
+                adam_clip_step(opt, c["MAX_GRAD_NORM"][i])
+            else:
+                torch.nn.utils.clip_grad_norm_(net.parameters(), c["MAX_GRAD_NORM"][i])
+                opt.step()
+        return [torch.stack([x.detach() for x in out]) for out in outs]
+
+    def _zero_grads(self) -> None:
+        for opt in self.opts:
+            opt.zero_grad(set_to_none=True)
+
+    def _joint_minibatch(self) -> List[torch.Tensor]:
+        """``_minibatch`` for the joint step: eager, or two warm-ups on a side stream, one capture, replays."""
+        j = self._joint
+        if not self.graphs:
+            self._zero_grads()
+            return self._joint_step()
+        if j["graph"] is None and j["warm"] < 2:
+            side = torch.cuda.Stream(self.device)
+            side.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(side):
+                self._zero_grads()
+                r = self._joint_step()
+            torch.cuda.current_stream(self.device).wait_stream(side)
+            j["warm"] += 1
+            return r
+        if j["graph"] is None:
+            self._zero_grads()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                j["out"] = self._joint_step()
+            j["graph"] = g
+        j["graph"].replay()
+        return [o.clone() for o in j["out"]]
+
+    def _prepare(self, i: int, h0: torch.Tensor) -> Dict:
+        """After the rollout: agent type i's last value, GAE and the static inputs of its minibatch steps."""
+        c, net, b = self.c, self.nets[i], self.buf[i]
+        st = self._static(i, self.n_actors[i], c["NUM_MINIBATCHES"])
+        with torch.no_grad():
+            _, _, last_val = net.step(self.h[i], self.last_obs[i], self.last_done[i])
+            gae_fn = gae_fused if self.fused_loss else calculate_gae
+            adv, targets = gae_fn(b.reward, b.value, b.global_done, last_val, c["GAMMA"][i], c["GAE_LAMBDA"][i])
+            st["h0"].copy_(h0); st["adv"].copy_(adv); st["tgt"].copy_(targets)
+        return st
+
+    def _set_lr(self, i: int) -> None:
+        """Agent type i's annealed learning rate for its next optimiser step, from its own ``opt_count``."""
+        c = self.c
+        if c["ANNEAL_LR"][i]:
+            lr = linear_schedule(c["LR"][i], self.opt_count[i], c["NUM_MINIBATCHES"], c["UPDATE_EPOCHS"],
+                                 self.num_updates)
+            for g in self.opts[i].param_groups:
+                if torch.is_tensor(g["lr"]):
+                    g["lr"].fill_(lr)
+                else:
+                    g["lr"] = lr
+
+    def _update_joint(self, h0: List[torch.Tensor]) -> List[torch.Tensor]:
+        """GROUPED_SCAN: every type's minibatch steps in lockstep; returns the types' summed loss scalars.
+        The permutations are drawn up front in the order the per-type path draws them (type 0's epochs,
+        then type 1's, ...), so the generator goes through the same sequence."""
+        c, nt, mb = self.c, self.n_types, self.c["NUM_MINIBATCHES"]
+        for i in range(nt):
+            self._prepare(i, h0[i])
+        perms = [[torch.randperm(n, device=self.device, generator=self.gen).view(mb, n // mb)
+                  for _ in range(c["UPDATE_EPOCHS"])] for n in self.n_actors]
+        stats = [torch.zeros(6, device=self.device) for _ in range(nt)]
+        for e in range(c["UPDATE_EPOCHS"]):
+            for m in range(mb):
+                for i in range(nt):
+                    self._set_lr(i)
+                    self._st[i]["idx"].copy_(perms[i][e][m])
+                for i, r in enumerate(self._joint_minibatch()):
+                    stats[i] += r
+                    self.opt_count[i] += 1
+        return stats
+
     def update(self) -> Dict:
         """One _update_step: rollout, GAE, UPDATE_EPOCHS x NUM_MINIBATCHES PPO steps per agent type."""
         c = self.c
         h0 = [h.clone() for h in self.h]
         self.rollout()
         metrics = {"loss": [], "avg_reward": []}
+        joint = self._update_joint(h0) if self.grouped_scan else None
         for i, net in enumerate(self.nets):
             b = self.buf[i]
             n, mb = self.n_actors[i], c["NUM_MINIBATCHES"]
-            st = self._static(i, n, mb)
-            with torch.no_grad():
-                _, _, last_val = net.step(self.h[i], self.last_obs[i], self.last_done[i])
-                gae_fn = gae_fused if self.fused_loss else calculate_gae
-                adv, targets = gae_fn(b.reward, b.value, b.global_done, last_val, c["GAMMA"][i], c["GAE_LAMBDA"][i])
-                st["h0"].copy_(h0[i]); st["adv"].copy_(adv); st["tgt"].copy_(targets)
-            stats = torch.zeros(6, device=self.device)
-            for _ in range(c["UPDATE_EPOCHS"]):
-                perm = torch.randperm(n, device=self.device, generator=self.gen)
-                for idx in perm.view(mb, n // mb):
-                    if c["ANNEAL_LR"][i]:
-                        lr = linear_schedule(c["LR"][i], self.opt_count[i], mb, c["UPDATE_EPOCHS"], self.num_updates)
-                        for g in self.opts[i].param_groups:
-                            if torch.is_tensor(g["lr"]):
-                                g["lr"].fill_(lr)
-                            else:
-                                g["lr"] = lr
-                    st["idx"].copy_(idx)
-                    stats += self._minibatch(i)
-                    self.opt_count[i] += 1
+            if joint is not None:
+                stats = joint[i]
+            else:
+                st = self._prepare(i, h0[i])
+                stats = torch.zeros(6, device=self.device)
+                for _ in range(c["UPDATE_EPOCHS"]):
+                    perm = torch.randperm(n, device=self.device, generator=self.gen)
+                    for idx in perm.view(mb, n // mb):
+                        self._set_lr(i)
+                        st["idx"].copy_(idx)
+                        stats += self._minibatch(i)
+                        self.opt_count[i] += 1
             stats /= c["UPDATE_EPOCHS"] * mb
             metrics["loss"].append(dict(zip(("total_loss", "value_loss", "actor_loss", "entropy", "approx_kl",
                                              "clip_frac"), stats)))
@@ -570,7 +699,7 @@ class IPPOTrainer:
     def load_checkpoint(self, path: str) -> None:
         """Restores what ``save_checkpoint`` wrote into this trainer (same env and sizes).  The
         parameters are copied in place (a captured rollout stays valid); the optimisers get new
-        state tensors, so the minibatch graphs are captured again at the next update."""
+        state tensors, so the minibatch graphs (the joint one included) are captured again at the next update."""
         ck = _read_checkpoint(path)
         if len(ck["nets"]) != self.n_types:
             raise ValueError(f"{path}: {len(ck['nets'])} agent types, this trainer has {self.n_types}")
@@ -587,6 +716,7 @@ class IPPOTrainer:
         for st in getattr(self, "_st", []):
             if st is not None:
                 st.update(warm=0, graph=None, out=None)
+        self._joint.update(warm=0, graph=None, out=None)
 
 
 CHECKPOINT_FORMAT = "hftlob-ippo-1"
@@ -642,7 +772,8 @@ def train(env: MARLEnv, config: Dict, n_updates: Optional[int] = None, dist=None
 
 
 def main(argv=None) -> None:
-    """python -m hftlob.train.ippo [--rl-config ippo.yaml] [--env-config 2_player_fq_fqc] [--updates N]"""
+    """python -m hftlob.train.ippo [--rl-config ippo.yaml] [--env-config 2_player_fq_fqc] [--updates N]
+    [--fused-gru] [--fused-policy] [--fused-loss] [--fused-opt] [--grouped-scan]"""
     import argparse
     import json
     import yaml
@@ -659,6 +790,9 @@ def main(argv=None) -> None:
                     help="the update's GAE and PPO loss (with its gradient) as fused HIP launches")
     ap.add_argument("--fused-opt", action="store_true",
                     help="the minibatch step's global-norm clip and Adam step as two fused HIP launches")
+    ap.add_argument("--grouped-scan", action="store_true",
+                    help="the agent types' minibatch steps in lockstep, their GRU scans one HIP launch per direction "
+                         "(needs --fused-gru)")
     ap.add_argument("--calc-eval", action="store_true",
                     help="CALC_EVAL: after every update NUM_STEPS_EVAL sampled steps in a separate eval env (the same "
                          "config, a synthetic day of another seed), logged as avg_reward_eval")
@@ -679,6 +813,8 @@ def main(argv=None) -> None:
         c["FUSED_LOSS"] = True
     if a.fused_opt:
         c["FUSED_OPT"] = True
+    if a.grouped_scan:
+        c["GROUPED_SCAN"] = True
     if a.calc_eval:
         c["CALC_EVAL"] = True
     cfg = (load_config_from_file(a.env_config) if a.env_config.endswith((".json", ".yaml"))

@@ -10,7 +10,12 @@ A minibatch step is the run of kernels that ends with k_adam_update; steps whose
 rollout, GAE or env kernel are left out.  The steps are grouped by their kernel count (the two agent
 types differ by one kernel) and the two commonest groups are summarised: kernel time per step by bucket
 (scan forward / backward, rocBLAS GEMMs, gathers and copies, loss, optimiser step, rest) and by kernel
-name, and the window from the step's first start to its last end."""
+name, and the window from the step's first start to its last end.
+
+With --grouped-scan in the traced command the same rule cuts a joint step of all agent types in two: the
+kernels up to the first type's k_adam_update (every type's forward, loss and backward, with the grouped
+scan launches, and the first type's optimiser step) and the two optimiser kernels of each further type;
+the two commonest groups are then those two parts."""
 import collections
 import csv
 import glob
