@@ -119,6 +119,66 @@ def test_rows_past_B_are_not_written():
         assert_close(name, buf[:rows].view(ref[name].shape), ref[name])
 
 
+@functools.lru_cache(maxsize=None)
+def saturated_case(H, kind):
+    """case(6, 17, H, False) with saturated gates and its float64 reference, not modified by the tests.
+    "hard": in rows b < 12 of every step the block b % 3 of gi (r, z or n) is +100 where (b // 3) % 2 == 0
+    and -100 otherwise, so expf(-x) overflows to inf or underflows to 0 inside the sigmoid and the gate is
+    exactly 0 or 1 in float32.  "scale4": gi and w_hh times 4.  Also returns the share of the bound that
+    a float32 torch loop on the CPU uses, over every output."""
+    T, B = 6, 17
+    x = {k: v.clone() for k, v in case(T, B, H, False)[0].items()}
+    if kind == "hard":
+        for b in range(12):
+            blk = b % 3
+            x["gi"][:, b, blk * H:(blk + 1) * H] = 100.0 if (b // 3) % 2 == 0 else -100.0
+    else:
+        x["gi"] *= 4.0
+        x["w_hh"] *= 4.0
+
+    def restate(d):
+        hseq, gates = G.gru_scan_reference(d["gi"], d["h0"], d["done"], d["w_hh"], d["b_hh"])
+        d_gi, d_gh_n, d_h0 = G.gru_scan_backward_reference(d["d_hseq"], hseq, gates, d["h0"], d["done"], d["w_hh"])
+        return dict(hseq=hseq, gates=gates, d_gi=d_gi, d_gh_n=d_gh_n, d_h0=d_h0)
+
+    ref = restate({k: (v.double() if v.dtype == torch.float32 else v) for k, v in x.items()})
+    f32 = restate(x)
+    share = 0.0
+    for k, r in ref.items():
+        assert bool(torch.isfinite(f32[k]).all()), k
+        bound = 1e-5 * r.abs() + 1e-5 * float(r.abs().max())
+        share = max(share, float(((f32[k].double() - r).abs() / bound).max()))
+    exact = int(((f32["gates"][..., :2 * H] == 0.0) | (f32["gates"][..., :2 * H] == 1.0)).sum())
+    return x, ref, share, exact
+
+
+def _saturated_run(H, kind):
+    x, ref, share, exact = saturated_case(H, kind)
+    print(f"float32 CPU restatement: {share:.4f} of the bound; {exact} r and z gates are exactly 0 or 1 in float32")
+    c = dev(x)
+    hseq, gates = G.scan_forward(c["gi"], c["h0"], c["done"], c["w_hh"], c["b_hh"], save_gates=True)
+    d_gi, d_gh_n, d_h0 = G.scan_backward(c["d_hseq"], hseq, gates, c["h0"], c["done"], c["w_hh"])
+    for name, got in (("hseq", hseq), ("gates", gates), ("d_gi", d_gi), ("d_gh_n", d_gh_n), ("d_h0", d_h0)):
+        assert bool(torch.isfinite(got).all()), f"{name}: not finite"
+        assert_close(name, got, ref[name])
+    return share, exact
+
+
+@pytest.mark.parametrize("H", [64, 128, 256])
+def test_hard_saturated_gates(H):
+    """sigmoidf_ is 1 / (1 + expf(-x)): at x = -100 expf overflows to inf and the gate must be 0, not NaN.
+    The forward with gates, then the backward on the forward's own outputs, against float64."""
+    share, exact = _saturated_run(H, "hard")
+    assert share <= 0.25 and exact >= 1000                             # conditions on the fixture, from the CPU
+
+
+def test_saturated_gates_at_scale_4():
+    """gi and w_hh times 4 at H = 128: gate inputs of some tens, where 1 - z cancels but nothing overflows.
+    (The float32 CPU loop uses 0.10 of the bound here, 0.17 at H = 64 and 0.23 at H = 256.)"""
+    share, _ = _saturated_run(128, "scale4")
+    assert share <= 0.25
+
+
 def _net_and_batch(seed=0):
     torch.manual_seed(seed)
     net = I.ActorCriticRNN(6, 5, 64, 64).cuda()
