@@ -4138,12 +4138,8 @@ __global__ __launch_bounds__(64) void k_env_step(hftlob_env_cfg c, int n_env, in
 // (one wave) runs its n_steps steps back to back, so no step boundary waits for the
 // batch's slowest env (a wave that finishes a step starts its next one at once).
 // Each wave carries its own copy of the master-key chain.  The step body is the
-// same env_step_dev as k_env_step; per-iteration opaque copies of the config and
-// base pointers keep LICM from hoisting the body's invariant loads and addresses
-// out of the step loop (they would stay live across it and double the registers):
-// the config pointer stays in the constant address space, so its fields are
-// still scalar loads, re-issued once per step.  (Never take &c: that copies the
-// struct to scratch.)
+// same env_step_dev as k_env_step, inside the loop that all four rollout kernels
+// share (rollout_loop below).
 typedef const __attribute__((address_space(4))) hftlob_env_cfg kcfg_t;
 
 // Issue priority by projected finish.  An env's work over a rollout depends on its data windows
@@ -4177,6 +4173,12 @@ DEV unsigned long long* wave_row(u32 hwid, u32 xcc, u32& slot) {
 #ifndef HFTLOB_PRIO_SCOPE
 #define HFTLOB_PRIO_SCOPE __HIP_MEMORY_SCOPE_WORKGROUP
 #endif
+#ifndef HFTLOB_BALANCE_EVERY
+#define HFTLOB_BALANCE_EVERY 1
+#endif
+#ifndef HFTLOB_BALANCE_MIN_ENVS
+#define HFTLOB_BALANCE_MIN_ENVS 1024
+#endif
 DEV void balance_prio(unsigned long long* row, u32 slot, unsigned long long r0, int done, int left) {
     const int l = lane_id();
     const unsigned long long now = __builtin_amdgcn_s_memrealtime();
@@ -4195,6 +4197,112 @@ DEV void balance_prio(unsigned long long* row, u32 slot, unsigned long long r0, 
     else if (q == 2) __builtin_amdgcn_s_setprio(1);
     else __builtin_amdgcn_s_setprio(0);
 }
+// A wave's issue-priority state over its rollout: begin() before the first step, after_step() at the
+// end of step t, end() after the last.  (-DHFTLOB_NO_BALANCE, an A/B build: all three do nothing.)
+struct Balance {
+#ifndef HFTLOB_NO_BALANCE
+    unsigned long long r0, *row;
+    u32 slot;
+    DEV void begin() {
+        r0 = __builtin_amdgcn_s_memrealtime();
+        const u32 hwid = __builtin_amdgcn_s_getreg(0xF804), xcc = __builtin_amdgcn_s_getreg(0x7814);
+        row = wave_row(hwid, xcc, slot);
+    }
+    DEV void after_step(int t, int n_steps, int n_env) {
+        // (a launch of at most one wave per SIMD, 4 x 256 on MI355X, has nothing to rank: C2 / C5 / C1)
+        if ((t + 1 < n_steps) && ((t % HFTLOB_BALANCE_EVERY) == 0) && (n_env > HFTLOB_BALANCE_MIN_ENVS))
+            balance_prio(row, slot, r0, t + 1, n_steps - t - 1);
+    }
+    // the wave is done: its slot's entry becomes a past time, so no neighbour counts it as live
+    DEV void end() {
+        if (lane_id() == 0) __hip_atomic_store(row + slot, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, HFTLOB_PRIO_SCOPE);
+    }
+#else
+    DEV void begin() {}
+    DEV void after_step(int, int, int) {}
+    DEV void end() {}
+#endif
+};
+
+// The persistent loop of the rollout kernels: one wave per env, its n_steps steps back to back.
+// rollout_loop calls step(Q, s) for every step s.t; the callable is the kernel's own step body around
+// env_step_dev (which takes s.in_lds(), s.keep() and s.fl).  The callable MUST end with
+// s.stepped(reset) and s.balance(): the loop makes neither call itself, because the priority update
+// made after the callable returned compiled to more SGPR spills and scratch bytes (cross-compiled
+// trial), and no test can see a forgotten s.balance(), since no result depends on the ranking.
+// k_env_rollout_actions, k_env_rollout_eval and k_env_rollout_eval_drawn run on this loop.
+// k_env_rollout writes the same loop out beside its key batches and diagnostics, with the same
+// Balance: on this loop its four-slot-set instantiation took 16 more scratch bytes
+// (profiles/rollout_loop_metadata.txt).  The rules, for all four:
+//  - Q is std::true_type for a step whose outputs are not emitted.  The quiet steps (`quiet`: every
+//    step but the last; otherwise none) run in a loop of their own, then the emitting ones in a
+//    second loop: the quiet copy of the step body holds no observation / reward-value code, and the
+//    constants the emitting copy keeps in registers are not live across the quiet loop.  TALLY (the
+//    evaluation kernels, whose quiet step is the tally step): always quiet (`quiet` is not read),
+//    and the last step is one emitting call, not a loop.  Neither loop is unrolled.
+//  - s.cp, s.st, s.md, s.is (TALLY: and s.sp, of `stats`, which the others pass as nullptr and never
+//    read) are per-step opaque copies of the config pointer and the base pointers: they keep LICM from hoisting the body's invariant loads and addresses out of
+//    the step loop (they would stay live across it and double the registers).  The config is the
+//    first kernel argument, offset 0 of the kernarg segment, and its pointer stays in the constant
+//    address space, so its fields are still scalar loads, re-issued once per step.  Never take &c:
+//    that copies the struct to scratch.
+//  - resident: the book stays in LDS from one step to the next (stored to the record only by the
+//    last step); an auto-reset rewrites the record, and the step after it loads the book from there.
+//    The 100/100 instantiation (NFIX > 0) only: in the general-size ones the AMDGPU backend moved the
+//    lane masks of the resident branch to VGPRs, which s_ff1's SGPR operand cannot take.  uni() makes
+//    the flag uniform: the divergence analysis cannot see that through the reset's lane loops.
+template <int NFIX>
+struct RolloutStep {
+    kcfg_t* cp;
+    i32* st;
+    const i32* md;
+    const i32* is;
+    double* sp;
+    int t, n_steps, n_env;
+    bool resident;
+    u32 fl;  // (env_step_dev's flags word, carried from step to step)
+    Balance bal;
+    DEV const hftlob_env_cfg& cfg() const { return *(const hftlob_env_cfg*)cp; }
+    DEV bool in_lds() const { return NFIX > 0 && resident; }
+    DEV bool keep() const { return NFIX > 0 && t + 1 < n_steps; }
+    DEV void stepped(bool reset) { resident = uni(!reset) != 0; }
+    DEV void balance() { bal.after_step(t, n_steps, n_env); }
+};
+template <int NFIX, bool TALLY, class Step>
+DEV void rollout_loop(int n_env, int n_steps, bool quiet, i32* state, const i32* msg_data, const i32* init_states,
+                      double* stats, Step&& step) {
+    kcfg_t* kp = (kcfg_t*)__builtin_amdgcn_kernarg_segment_ptr();
+    RolloutStep<NFIX> s;
+    s.n_steps = n_steps;
+    s.n_env = n_env;
+    s.resident = false;
+    s.fl = 0;
+    s.bal.begin();
+    auto one = [&](auto Q, int t) {
+        s.t = t;
+        s.cp = kp;
+        s.st = state;
+        s.md = msg_data;
+        s.is = init_states;
+        s.sp = stats;
+        if constexpr (TALLY) asm volatile("" : "+s"(s.cp), "+s"(s.st), "+s"(s.md), "+s"(s.is), "+s"(s.sp));
+        else asm volatile("" : "+s"(s.cp), "+s"(s.st), "+s"(s.md), "+s"(s.is));
+        step(Q, s);
+    };
+    int t = 0;
+    if (TALLY || quiet) {
+#pragma unroll 1
+        for (; t + 1 < n_steps; ++t) one(std::true_type{}, t);
+    }
+    if constexpr (TALLY) {
+        one(std::false_type{}, t);
+    } else {
+#pragma unroll 1
+        for (; t < n_steps; ++t) one(std::false_type{}, t);
+    }
+    s.bal.end();
+}
+
 // KB: 1 = the config derives its step keys in batches (kb_ok, checked by the launch code), 0 = it
 // does not, -1 = decided at run time (the general-size and rows-alias instantiations).  The metric
 // kernel is KB = 1: its loop holds no per-step key derivation.
@@ -4215,18 +4323,10 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout(hftlob_env_cfg c_arg, int
     Key mk{master[0], master[1]};
     // `c` is the first kernel argument: offset 0 of the kernarg segment (constant address space)
     kcfg_t* kp = (kcfg_t*)__builtin_amdgcn_kernarg_segment_ptr();
-    // the book stays in LDS from one step to the next (stored to the record only by the last
-    // step); an auto-reset rewrites the record, and the step after it loads the book from there.
-    // (The 100/100 instantiation only: in the general-size ones the AMDGPU backend moved the
-    // lane masks of the resident branch to VGPRs, which s_ff1's SGPR operand cannot take.)
     bool resident = false;
     u32 fl = 0;
-#ifndef HFTLOB_NO_BALANCE
-    const unsigned long long bal_r0 = __builtin_amdgcn_s_memrealtime();
-    const u32 bal_hwid = __builtin_amdgcn_s_getreg(0xF804), bal_xcc = __builtin_amdgcn_s_getreg(0x7814);
-    u32 bal_slot;
-    unsigned long long* bal_row = wave_row(bal_hwid, bal_xcc, bal_slot);
-#endif
+    Balance bal;
+    bal.begin();
 #ifdef HFTLOB_WAVETIME
     // diagnostic build only (tools/diag_wavetime.py): the wave's start time and hardware slot,
     // then each step's end time, into the per-step info rows (words 0..9 of row (t, e))
@@ -4238,11 +4338,7 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout(hftlob_env_cfg c_arg, int
     const bool kbat = KB < 0 ? kb_ok(c) : KB == 1;
     const int kbw = kb_words(c);
     i32* kbuf = lds + lds_map(c, NFIX > 0 ? NFIX : c.lob.n_orders, NFIX > 0 ? NFIX : c.lob.n_trades, RA).kb;
-    // one step of the rollout: Q = true for a step whose outputs are not emitted (per_step = 0, not
-    // the last step).  The quiet steps run in a loop of their own, then the emitted ones (per_step =
-    // 1: all steps; 0: the last one) in a second loop: the quiet copy of the step body holds no
-    // observation / reward-value code, and the constants the emitting copy keeps in registers are
-    // not live across the quiet loop
+    // one step, under rollout_loop's rules (Q, the opaque copies, resident)
     auto step = [&](auto Q, int t) {
         constexpr bool QT = decltype(Q)::value;
         const size_t o = per_step ? (size_t)t * n_env : 0;
@@ -4272,19 +4368,9 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout(hftlob_env_cfg c_arg, int
             ox && out.msgs ? out.msgs + o * cc.n_msgs * 8 : nullptr,
             ox && out.debug ? out.debug + o * (size_t)HFTLOB_DEBUG_WORDS(cc.lob.n_trades) : nullptr, lds,
             NFIX > 0 && resident, NFIX > 0 && t + 1 < n_steps, fl, kbat ? kbuf + tb * kbw : nullptr, !QT);
-        resident = uni(!reset) != 0;  // (uniform: the divergence analysis cannot see it through the reset's lane loops)
+        resident = uni(!reset) != 0;
         STAMP(bp0);
-#ifndef HFTLOB_NO_BALANCE
-#ifndef HFTLOB_BALANCE_EVERY
-#define HFTLOB_BALANCE_EVERY 1
-#endif
-#ifndef HFTLOB_BALANCE_MIN_ENVS
-#define HFTLOB_BALANCE_MIN_ENVS 1024
-#endif
-        // (a launch of at most one wave per SIMD, 4 x 256 on MI355X, has nothing to rank: C2 / C5 / C1)
-        if ((t + 1 < n_steps) && ((t % HFTLOB_BALANCE_EVERY) == 0) && (n_env > HFTLOB_BALANCE_MIN_ENVS))
-            balance_prio(bal_row, bal_slot, bal_r0, t + 1, n_steps - t - 1);
-#endif
+        bal.after_step(t, n_steps, n_env);
 #ifdef HFTLOB_STAMPS
         // rollout-only phases beside env_step_dev's stamps: the step-key batch (every KB_STEPS-th
         // step) and the issue-priority update, words 16 / 17 of the step's info row
@@ -4314,22 +4400,16 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout(hftlob_env_cfg c_arg, int
     if (!per_step) {
 #endif
 #pragma unroll 1
-        for (; t + 1 < n_steps; ++t) step(std::integral_constant<bool, true>{}, t);
+        for (; t + 1 < n_steps; ++t) step(std::true_type{}, t);
     }
 #pragma unroll 1
-    for (; t < n_steps; ++t) step(std::integral_constant<bool, false>{}, t);
-#ifndef HFTLOB_NO_BALANCE
-    // the wave is done: its slot's entry becomes a past time, so no neighbour counts it as live
-    if (lane_id() == 0) __hip_atomic_store(bal_row + bal_slot, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
-                                           HFTLOB_PRIO_SCOPE);
-#endif
+    for (; t < n_steps; ++t) step(std::false_type{}, t);
+    bal.end();
     if ((e == 0) && (lane_id() == 0)) { master_out[0] = mk.a; master_out[1] = mk.b; }
 }
 
 // n_steps MARLEnv.step calls with the CALLER's keys and actions in one launch (hftlob_env_rollout_actions):
-// k_env_rollout's persistent structure (one wave per env, its steps back to back, the book resident
-// in LDS in the 100/100 instantiation, a quiet loop for the steps whose outputs nobody reads, issue
-// priority by projected finish) around the step body's master = false mode: step t reads row t of
+// rollout_loop around the step body's master = false mode: step t reads row t of
 // keys [n_steps][n_env][2] and of actions [n_steps][n_env][action_words] and writes neither.  No
 // master-key chain, so no key batches either (their LDS words after the book stay unused) and no
 // master_out store.  Bit for bit n_steps k_env_step launches over the same rows.
@@ -4345,56 +4425,25 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout_actions(hftlob_env_cfg c,
     const int e = blockIdx.x;
     if (e >= n_env) return;
     Key mk{0u, 0u};  // (env_step_dev's master-key reference: never read with master = false)
-    // `c` is the first kernel argument: offset 0 of the kernarg segment (constant address space)
-    kcfg_t* kp = (kcfg_t*)__builtin_amdgcn_kernarg_segment_ptr();
-    bool resident = false;  // (the 100/100 instantiation only, as in k_env_rollout)
-    u32 fl = 0;
-#ifndef HFTLOB_NO_BALANCE
-    const unsigned long long bal_r0 = __builtin_amdgcn_s_memrealtime();
-    const u32 bal_hwid = __builtin_amdgcn_s_getreg(0xF804), bal_xcc = __builtin_amdgcn_s_getreg(0x7814);
-    u32 bal_slot;
-    unsigned long long* bal_row = wave_row(bal_hwid, bal_xcc, bal_slot);
-#endif
-    // one step: Q = true for a step whose outputs are not emitted (per_step = 0, not the last step);
-    // the per-step opaque copies of the config and base pointers keep the body's invariants out of
-    // the step loop's preheader (see k_env_rollout)
-    auto step = [&](auto Q, int t) {
+    // (per_step = 1 emits all steps, 0 the last one)
+    rollout_loop<NFIX, false>(n_env, n_steps, !per_step, state, msg_data, init_states, nullptr, [&](auto Q, auto& s) {
         constexpr bool QT = decltype(Q)::value;
+        const int t = s.t;
         const size_t o = per_step ? (size_t)t * n_env : 0;
-        kcfg_t* cp = kp;
-        i32* st = state;
-        const i32* md = msg_data;
-        const i32* is = init_states;
-        asm volatile("" : "+s"(cp), "+s"(st), "+s"(md), "+s"(is));
-        const hftlob_env_cfg& cc = *(const hftlob_env_cfg*)cp;
+        const hftlob_env_cfg& cc = s.cfg();
         const bool ox = !QT;  // (the optional outputs: written by the emitted steps only)
         const bool reset = env_step_dev<S, NFIX, RC, RA, QT, /*PK=*/0>(
             cc, n_env, e, e, keys + (size_t)t * n_env * 2, false, mk,
-            const_cast<i32*>(actions) + (size_t)t * n_env * cc.action_words, md, is, st,
+            const_cast<i32*>(actions) + (size_t)t * n_env * cc.action_words, s.md, s.is, s.st,
             out.obs + o * cc.n_agents * cc.obs_stride, out.rewards + o * cc.n_agents, out.done_all + o,
             out.dones + o * cc.n_agents, ox && out.info ? out.info + o * cc.info_words : nullptr,
             ox && out.obs_raw ? out.obs_raw + o * cc.n_agents * cc.obs_stride : nullptr,
             ox && out.msgs ? out.msgs + o * cc.n_msgs * 8 : nullptr,
             ox && out.debug ? out.debug + o * (size_t)HFTLOB_DEBUG_WORDS(cc.lob.n_trades) : nullptr, lds,
-            NFIX > 0 && resident, NFIX > 0 && t + 1 < n_steps, fl, nullptr, !QT);
-        resident = uni(!reset) != 0;  // (an auto-reset rewrote the record: the next step loads the book from it)
-#ifndef HFTLOB_NO_BALANCE
-        if ((t + 1 < n_steps) && ((t % HFTLOB_BALANCE_EVERY) == 0) && (n_env > HFTLOB_BALANCE_MIN_ENVS))
-            balance_prio(bal_row, bal_slot, bal_r0, t + 1, n_steps - t - 1);
-#endif
-    };
-    int t = 0;
-    if (!per_step) {
-#pragma unroll 1
-        for (; t + 1 < n_steps; ++t) step(std::integral_constant<bool, true>{}, t);
-    }
-#pragma unroll 1
-    for (; t < n_steps; ++t) step(std::integral_constant<bool, false>{}, t);
-#ifndef HFTLOB_NO_BALANCE
-    // the wave is done: its slot's entry becomes a past time, so no neighbour counts it as live
-    if (lane_id() == 0) __hip_atomic_store(bal_row + bal_slot, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
-                                           HFTLOB_PRIO_SCOPE);
-#endif
+            s.in_lds(), s.keep(), s.fl, nullptr, !QT);
+        s.stepped(reset);
+        s.balance();
+    });
 }
 
 // Fixed-action / scripted evaluation (hftlob_env_rollout_eval): k_env_rollout_actions' launch with
@@ -4417,47 +4466,20 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout_eval(hftlob_env_cfg c, in
     const int e = blockIdx.x;
     if (e >= n_env) return;
     Key mk{0u, 0u};  // (env_step_dev's master-key reference: never read with master = false)
-    kcfg_t* kp = (kcfg_t*)__builtin_amdgcn_kernarg_segment_ptr();
-    bool resident = false;  // (the 100/100 instantiation only, as in k_env_rollout)
-    u32 fl = 0;
-#ifndef HFTLOB_NO_BALANCE
-    const unsigned long long bal_r0 = __builtin_amdgcn_s_memrealtime();
-    const u32 bal_hwid = __builtin_amdgcn_s_getreg(0xF804), bal_xcc = __builtin_amdgcn_s_getreg(0x7814);
-    u32 bal_slot;
-    unsigned long long* bal_row = wave_row(bal_hwid, bal_xcc, bal_slot);
-#endif
-    // one step: Q = true for a tally step that emits nothing (every step but the last); the per-step
-    // opaque copies keep the body's invariants out of the step loop's preheader (see k_env_rollout)
-    auto step = [&](auto Q, int t) {
+    rollout_loop<NFIX, true>(n_env, n_steps, true, state, msg_data, init_states, stats, [&](auto Q, auto& s) {
         constexpr bool QT = decltype(Q)::value;
-        kcfg_t* cp = kp;
-        i32* st = state;
-        const i32* md = msg_data;
-        const i32* is = init_states;
-        double* sp = stats;
-        asm volatile("" : "+s"(cp), "+s"(st), "+s"(md), "+s"(is), "+s"(sp));
-        const hftlob_env_cfg& cc = *(const hftlob_env_cfg*)cp;
+        const int t = s.t;
+        const hftlob_env_cfg& cc = s.cfg();
         const bool ox = !QT;  // (the optional outputs: written by the emitted step only)
         const bool reset = env_step_dev<S, NFIX, RC, RA, QT, /*PK=*/0, /*TALLY=*/true>(
             cc, n_env, e, e, keys + (size_t)t * n_env * 2, false, mk,
-            const_cast<i32*>(actions) + (fixed ? (size_t)0 : (size_t)t * n_env * cc.action_words), md, is, st, out.obs,
+            const_cast<i32*>(actions) + (fixed ? (size_t)0 : (size_t)t * n_env * cc.action_words), s.md, s.is, s.st, out.obs,
             out.rewards, out.done_all, out.dones, ox ? out.info : nullptr, ox ? out.obs_raw : nullptr,
-            ox ? out.msgs : nullptr, ox ? out.debug : nullptr, lds, NFIX > 0 && resident, NFIX > 0 && t + 1 < n_steps, fl,
-            nullptr, !QT, sp, fixed ? 0 : -1);
-        resident = uni(!reset) != 0;  // (an auto-reset rewrote the record: the next step loads the book from it)
-#ifndef HFTLOB_NO_BALANCE
-        if ((t + 1 < n_steps) && ((t % HFTLOB_BALANCE_EVERY) == 0) && (n_env > HFTLOB_BALANCE_MIN_ENVS))
-            balance_prio(bal_row, bal_slot, bal_r0, t + 1, n_steps - t - 1);
-#endif
-    };
-    int t = 0;
-#pragma unroll 1
-    for (; t + 1 < n_steps; ++t) step(std::integral_constant<bool, true>{}, t);
-    step(std::integral_constant<bool, false>{}, t);
-#ifndef HFTLOB_NO_BALANCE
-    if (lane_id() == 0) __hip_atomic_store(bal_row + bal_slot, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
-                                           HFTLOB_PRIO_SCOPE);
-#endif
+            ox ? out.msgs : nullptr, ox ? out.debug : nullptr, lds, s.in_lds(), s.keep(), s.fl, nullptr, !QT, s.sp,
+            fixed ? 0 : -1);
+        s.stepped(reset);
+        s.balance();
+    });
 }
 
 // Drawn-baseline evaluation (hftlob_env_rollout_eval_drawn): k_env_rollout_eval whose actions are
@@ -4486,25 +4508,11 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout_eval_drawn(hftlob_env_cfg
     const int e = blockIdx.x;
     if (e >= n_env) return;
     Key mk{0u, 0u};  // (env_step_dev's master-key reference: never read with master = false)
-    kcfg_t* kp = (kcfg_t*)__builtin_amdgcn_kernarg_segment_ptr();
-    bool resident = false;  // (the 100/100 instantiation only, as in k_env_rollout)
-    u32 fl = 0;
-#ifndef HFTLOB_NO_BALANCE
-    const unsigned long long bal_r0 = __builtin_amdgcn_s_memrealtime();
-    const u32 bal_hwid = __builtin_amdgcn_s_getreg(0xF804), bal_xcc = __builtin_amdgcn_s_getreg(0x7814);
-    u32 bal_slot;
-    unsigned long long* bal_row = wave_row(bal_hwid, bal_xcc, bal_slot);
-#endif
-    // one step, as in k_env_rollout_eval, after the draw of its actions
-    auto step = [&](auto Q, int t) {
+    // k_env_rollout_eval's step after the draw of its actions
+    rollout_loop<NFIX, true>(n_env, n_steps, true, state, msg_data, init_states, stats, [&](auto Q, auto& s) {
         constexpr bool QT = decltype(Q)::value;
-        kcfg_t* cp = kp;
-        i32* st = state;
-        const i32* md = msg_data;
-        const i32* is = init_states;
-        double* sp = stats;
-        asm volatile("" : "+s"(cp), "+s"(st), "+s"(md), "+s"(is), "+s"(sp));
-        const hftlob_env_cfg& cc = *(const hftlob_env_cfg*)cp;
+        const int t = s.t;
+        const hftlob_env_cfg& cc = s.cfg();
         const int l = lane_id();
         i32 drawn = 0;
         {
@@ -4529,24 +4537,12 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout_eval_drawn(hftlob_env_cfg
         }
         const bool ox = !QT;  // (the optional outputs: written by the emitted step only)
         const bool reset = env_step_dev<S, NFIX, RC, RA, QT, /*PK=*/0, /*TALLY=*/true, /*BAKED=*/-1, /*DRAWN=*/true>(
-            cc, n_env, e, e, keys + (size_t)t * n_env * 2, false, mk, nullptr, md, is, st, out.obs, out.rewards,
+            cc, n_env, e, e, keys + (size_t)t * n_env * 2, false, mk, nullptr, s.md, s.is, s.st, out.obs, out.rewards,
             out.done_all, out.dones, ox ? out.info : nullptr, ox ? out.obs_raw : nullptr, ox ? out.msgs : nullptr,
-            ox ? out.debug : nullptr, lds, NFIX > 0 && resident, NFIX > 0 && t + 1 < n_steps, fl, nullptr, !QT, sp, -1,
-            drawn);
-        resident = uni(!reset) != 0;  // (an auto-reset rewrote the record: the next step loads the book from it)
-#ifndef HFTLOB_NO_BALANCE
-        if ((t + 1 < n_steps) && ((t % HFTLOB_BALANCE_EVERY) == 0) && (n_env > HFTLOB_BALANCE_MIN_ENVS))
-            balance_prio(bal_row, bal_slot, bal_r0, t + 1, n_steps - t - 1);
-#endif
-    };
-    int t = 0;
-#pragma unroll 1
-    for (; t + 1 < n_steps; ++t) step(std::integral_constant<bool, true>{}, t);
-    step(std::integral_constant<bool, false>{}, t);
-#ifndef HFTLOB_NO_BALANCE
-    if (lane_id() == 0) __hip_atomic_store(bal_row + bal_slot, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
-                                           HFTLOB_PRIO_SCOPE);
-#endif
+            ox ? out.debug : nullptr, lds, s.in_lds(), s.keep(), s.fl, nullptr, !QT, s.sp, -1, drawn);
+        s.stepped(reset);
+        s.balance();
+    });
 }
 
 // ==================================================== K3/K4: PRNG kernels
@@ -4969,16 +4965,22 @@ static int env_launch(const hftlob_env_cfg* cfg, int n_env, void* stream, Kernel
     });
     return listed ? launch_status() : fail(HFTLOB_ELAUNCH, "no kernel for the config's variant");
 }
+// env_launch's `kernel` for a kernel template K<S, NFIX, RC, RA> with an instantiation per listed variant
+#define LISTED_KERNEL(K) \
+    [](auto V, const Variant&) { return K<decltype(V)::S, decltype(V)::NFIX, decltype(V)::RC, decltype(V)::RA>; }
 }  // extern "C++"
+
+// the four outputs every step writes
+static int check_out(const hftlob_step_out* out) {
+    return out->obs && out->rewards && out->done_all && out->dones ? HFTLOB_OK : fail(HFTLOB_ENULL, "null output");
+}
 
 static int env_step_launch(const hftlob_env_cfg* cfg, int n_env, int key_e0, int key_n, const uint32_t* keys,
                            const uint32_t* key_in, uint32_t* key_out, int32_t* actions, const int32_t* msg_data,
                            const int32_t* init_states, int32_t* state, const hftlob_step_out* out, void* stream) {
-    if (!out->obs || !out->rewards || !out->done_all || !out->dones) return fail(HFTLOB_ENULL, "null output");
-    return env_launch(
-        cfg, n_env, stream,
-        [](auto V, const Variant&) { return k_env_step<decltype(V)::S, decltype(V)::NFIX, decltype(V)::RC, decltype(V)::RA>; },
-        key_e0, key_n, keys, key_in, key_out, actions, msg_data, init_states, state, *out);
+    if (int rc = check_out(out)) return rc;
+    return env_launch(cfg, n_env, stream, LISTED_KERNEL(k_env_step),
+                      key_e0, key_n, keys, key_in, key_out, actions, msg_data, init_states, state, *out);
 }
 
 // all n_steps of a rollout in one k_env_rollout launch (see there)
@@ -5140,7 +5142,7 @@ int hftlob_env_rollout_sampled(const hftlob_env_cfg* cfg, int n_env, int key_e0,
     if (n_env == 0 || n_steps == 0) return HFTLOB_OK;
     if (!key_in || !key_out || (n_slices > 0 && !key_scratch) || !msg_data || !init_states || !state || !out)
         return fail(HFTLOB_ENULL, "null array");
-    if (!out->obs || !out->rewards || !out->done_all || !out->dones) return fail(HFTLOB_ENULL, "null output");
+    if ((rc = check_out(out))) return rc;
     if (key_in == key_out) return fail(HFTLOB_EINVAL, "key_in and key_out must be distinct buffers");
     hipStream_t caller = (hipStream_t)stream;
     DeviceGuard dg;
@@ -5197,13 +5199,9 @@ int hftlob_env_rollout_actions(const hftlob_env_cfg* cfg, int n_env, int n_steps
     if (n_env < 0 || n_steps < 0) return fail(HFTLOB_ESHAPE, "negative n_env / n_steps");
     if (n_env == 0 || n_steps == 0) return HFTLOB_OK;
     if (!keys || !actions || !msg_data || !init_states || !state || !out) return fail(HFTLOB_ENULL, "null array");
-    if (!out->obs || !out->rewards || !out->done_all || !out->dones) return fail(HFTLOB_ENULL, "null output");
-    return env_launch(
-        cfg, n_env, stream,
-        [](auto V, const Variant&) {
-            return k_env_rollout_actions<decltype(V)::S, decltype(V)::NFIX, decltype(V)::RC, decltype(V)::RA>;
-        },
-        n_steps, per_step, keys, actions, msg_data, init_states, state, *out);
+    if ((rc = check_out(out))) return rc;
+    return env_launch(cfg, n_env, stream, LISTED_KERNEL(k_env_rollout_actions),
+                      n_steps, per_step, keys, actions, msg_data, init_states, state, *out);
 }
 
 int hftlob_env_rollout_eval(const hftlob_env_cfg* cfg, int n_env, int n_steps, const uint32_t* keys,
@@ -5215,13 +5213,9 @@ int hftlob_env_rollout_eval(const hftlob_env_cfg* cfg, int n_env, int n_steps, c
     // (the last step always emits and every step adds to stats: no empty call, unlike the rollouts above)
     if (n_env < 1 || n_steps < 1) return fail(HFTLOB_ESHAPE, "n_env and n_steps must be >= 1");
     if (!keys || !actions || !msg_data || !init_states || !state || !stats || !out) return fail(HFTLOB_ENULL, "null array");
-    if (!out->obs || !out->rewards || !out->done_all || !out->dones) return fail(HFTLOB_ENULL, "null output");
-    return env_launch(
-        cfg, n_env, stream,
-        [](auto V, const Variant&) {
-            return k_env_rollout_eval<decltype(V)::S, decltype(V)::NFIX, decltype(V)::RC, decltype(V)::RA>;
-        },
-        n_steps, actions_fixed != 0 ? 1 : 0, keys, actions, msg_data, init_states, state, stats, *out);
+    if ((rc = check_out(out))) return rc;
+    return env_launch(cfg, n_env, stream, LISTED_KERNEL(k_env_rollout_eval),
+                      n_steps, actions_fixed != 0 ? 1 : 0, keys, actions, msg_data, init_states, state, stats, *out);
 }
 
 int hftlob_env_rollout_eval_drawn(const hftlob_env_cfg* cfg, int n_env, int n_steps, const uint32_t* keys,
@@ -5233,7 +5227,7 @@ int hftlob_env_rollout_eval_drawn(const hftlob_env_cfg* cfg, int n_env, int n_st
     if (n_env < 1 || n_steps < 1) return fail(HFTLOB_ESHAPE, "n_env and n_steps must be >= 1");
     if (!keys || !draw_keys || !allowed || !msg_data || !init_states || !state || !stats || !out)
         return fail(HFTLOB_ENULL, "null array");
-    if (!out->obs || !out->rewards || !out->done_all || !out->dones) return fail(HFTLOB_ENULL, "null output");
+    if ((rc = check_out(out))) return rc;
     if (!cfg->prng_partitionable)
         return fail(HFTLOB_EINVAL, "rollout_eval_drawn: prng_partitionable is off; the draw is built for the partitionable threefry only");
     DrawMasks am;
@@ -5249,13 +5243,10 @@ int hftlob_env_rollout_eval_drawn(const hftlob_env_cfg* cfg, int n_env, int n_st
             return fail(HFTLOB_EINVAL, "rollout_eval_drawn: n_env * n_agents * n_actions of a type is past the 32-bit counter");
         am.m[t] = allowed[t];
     }
-    return env_launch(
-        cfg, n_env, stream,
-        [](auto V, const Variant&) {
-            return k_env_rollout_eval_drawn<decltype(V)::S, decltype(V)::NFIX, decltype(V)::RC, decltype(V)::RA>;
-        },
-        n_steps, keys, draw_keys, am, actions_out, msg_data, init_states, state, stats, *out);
+    return env_launch(cfg, n_env, stream, LISTED_KERNEL(k_env_rollout_eval_drawn),
+                      n_steps, keys, draw_keys, am, actions_out, msg_data, init_states, state, stats, *out);
 }
+#undef LISTED_KERNEL
 
 int hftlob_sample_actions(const hftlob_env_cfg* cfg, int n_env, const uint32_t* keys, int32_t* actions, void* stream) {
     if (!cfg) return fail(HFTLOB_ENULL, "null cfg");

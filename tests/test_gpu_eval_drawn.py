@@ -137,8 +137,8 @@ def drawn_case(tag, cfg, E, T, cuts, seed, entries=None):
     return _CASES[tag]
 
 
-def check_drawn_case(V, E, T, crosses=True):
-    env = V["env"]
+def check_device_paths(V, T):
+    """the bit-for-bit part of a case: the launch that draws against the other device paths"""
     assert V["acts"].dtype == torch.int32 and torch.equal(V["acts"], V["per_launch"]), \
         "actions_out vs hftlob_draw_actions per step and type"
     bad = torch.nonzero(V["state"] != V["ref_state"])
@@ -148,6 +148,10 @@ def check_drawn_case(V, E, T, crosses=True):
     assert _same(a["obs"], b["obs"]) and _same(a["rew"], b["rew"]) and _same(a["dones"], b["dones"])
     assert bool((a["done"] == b["done"]).all()) and bool((a["info"] == b["info"]).all())
     assert bool((V["stats"][:, :, 0] == T).all())
+
+
+def check_drawn_case(V, E, T, crosses=True):
+    check_device_paths(V, T)
     if crosses:
         assert bool((V["stats"][:, :, 1] >= 1).all()), "every env crossed its episode end"
     # the numpy definition over all steps: the rows with a clear gap, which must be nearly all
@@ -196,6 +200,15 @@ def test_rollout_eval_drawn_general_kernel_and_a_mixed_mask():
     check_drawn_case(V, 3, 8, crosses=False)
     got = V["acts"].cpu().numpy()
     assert set(np.unique(got[:, :, 0])) == {1, 4} and (got[:, :, 1] == 2).all()
+
+
+def test_rollout_eval_drawn_ranked_launch_and_one_step_launch():
+    """E = 1025, T = 3 in launches of 2 steps and 1: the smallest launch whose waves rank their issue
+    priority (after step 0 of the first launch), and a launch of the emitting step alone.  The device
+    paths only: the numpy definition's share of clear rows is not known at this shape."""
+    V = drawn_case("fq_fqc_1025", builtin_config(FQ), 1025, 3, (2, 1), seed=15)
+    _expect_launch(V["env"], NFIX)
+    check_device_paths(V, 3)
 
 
 def test_rollout_eval_drawn_without_actions_out_and_bad_arguments():

@@ -130,9 +130,11 @@ def test_resident_kernel_crosses_reset(per_step):
                            reset_inside=True)
 
 
-@pytest.mark.parametrize("E,T,per_step", [(8, 1, False), (8, 1, True), (1, 1, False), (1, 5, False), (1, 5, True)])
+@pytest.mark.parametrize("E,T,per_step", [(8, 1, False), (8, 1, True), (1, 1, False), (1, 5, False), (1, 5, True),
+                                          (1025, 3, False), (1025, 3, True)])
 def test_single_step_and_single_env(E, T, per_step):
-    """T = 1: the emitting loop alone, keep = false on the only step; E = 1: a one-workgroup launch"""
+    """T = 1: the emitting loop alone, keep = false on the only step; E = 1: a one-workgroup launch;
+    E = 1025: the smallest launch whose waves rank their issue priority, after steps 0 and 1 of T = 3"""
     rollout_actions_parity("fq_fqc", builtin_config("2_player_fq_fqc"), E, T, per_step, expect=NFIX)
 
 

@@ -143,9 +143,10 @@ def test_fixed_actions():
     assert bool((a[2][:, :, 0] == T).all()) and not bool((s0.buf == R["end"]).all())
 
 
-@pytest.mark.parametrize("E,T", [(8, 1), (1, 1), (1, 5)])
+@pytest.mark.parametrize("E,T", [(8, 1), (1, 1), (1, 5), (1025, 3)])
 def test_single_step_and_single_env(E, T):
-    """T = 1: the emitting step alone is tallied; E = 1: a one-workgroup launch"""
+    """T = 1: the emitting step alone is tallied; E = 1: a one-workgroup launch; E = 1025: the smallest
+    launch whose waves rank their issue priority, after the tally steps 0 and 1 of T = 3"""
     eval_parity("fq_fqc", builtin_config(FQ), E, T, expect=NFIX)
 
 
