@@ -782,6 +782,43 @@ int hftlob_adam_clip(int n_tensors, const hftlob_adam_tensor* tensors /*[n_tenso
                      float max_norm, double* workspace /*HFTLOB_ADAM_WORKSPACE doubles*/,
                      float* total_norm /*device, one float, or NULL*/, void* stream);
 
+/* The weight and bias gradients of the learner's narrow layers: a product reduced over many rows into a
+ * small output, float32, row-major, contiguous,
+ *       C[P][Q]  = sum_n A[n][p] B[n][q]          A [N][P], B [N][Q]
+ *       sum_a[P] = sum_n A[n][p]                  (NULL to skip)
+ *       sum_b[Q] = sum_n B[n][q]                  (NULL to skip)
+ * for 1 <= P <= HFTLOB_XTY_MAX_P (any value), Q 64, 128 or 256, N >= 0.  For a linear layer y = x W^T + b
+ * with a narrow output (W [P][Q]) A = d_y, B = x give d_W = C and d_b = sum_a; with a narrow input
+ * (W [Q][P]) A = x, B = d_y give d_W = C^T and d_b = sum_b.  Two launches on the caller's stream:
+ *   the partial pass cuts the rows into G contiguous stripes, one per workgroup (and per 16 rows of C).
+ *     The stripe rule is a function of N alone, with R = HFTLOB_XTY_STRIPE_ROWS, M = HFTLOB_XTY_MAX_STRIPES:
+ *         rows = R if ceil(N / R) <= M, else ceil(N / M)        G = ceil(N / rows)
+ *     stripe g is the rows [g rows, min(N, (g + 1) rows)): up to M stripes of R rows, and past M R rows
+ *     the stripes grow instead of their number; none is empty.  Inside a stripe each of a workgroup's four
+ *     waves takes every fourth row and adds a[p] b[q] with one fused multiply-add (fmaf) per row, in row
+ *     order; the four sums are added in wave order.  The workgroup leaves its float32 partial in the
+ *     workspace: per stripe P Q + P + Q floats, [P][Q] of C, then sum_a's, then sum_b's (the sums' only
+ *     when asked for);
+ *   the final pass adds the G partials of every output element in double, in stripe order inside each of
+ *     16 consecutive groups of ceil(G / 16) stripes, then the 16 group sums in group order, and rounds
+ *     once to float32.
+ * No floating-point atomic and a fixed order of every sum: the same inputs give the same bits on every
+ * call, eager or replayed from a HIP graph, and C's bits do not depend on which sums are asked for.
+ * Rows past N and columns past P or Q are never read.  workspace is the caller's, hftlob_xty_workspace(N,
+ * P, Q) floats (G (P Q + P + Q); a host-only function that makes no device call), written before it is
+ * read.  N = 0 zero-fills C and the sums that are not NULL with asynchronous memsets and reads nothing: A, B
+ * and workspace may then be NULL.  The call neither allocates nor synchronises and can be captured in a HIP
+ * graph.  Checked in this order, before any device work: HFTLOB_ESHAPE: P outside 1..HFTLOB_XTY_MAX_P, Q not
+ * 64, 128 or 256, N < 0 (hftlob_xty_workspace returns the same code, as a negative size); HFTLOB_ENULL: a NULL
+ * C, or with N > 0 a NULL A, B or workspace; HFTLOB_EINVAL: with N > 0 a B that is not 16-byte aligned. */
+#define HFTLOB_XTY_MAX_P 64
+#define HFTLOB_XTY_STRIPE_ROWS 128    /* R: the rows of a stripe up to HFTLOB_XTY_MAX_STRIPES stripes */
+#define HFTLOB_XTY_MAX_STRIPES 512    /* M: the most stripes (workgroups per 16 rows of C) */
+long long hftlob_xty_workspace(long long N, int P, int Q);   /* floats; < 0: an error code */
+int hftlob_xty(long long N, int P, int Q, const float* A /*[N][P]*/, const float* B /*[N][Q]*/,
+               float* C /*[P][Q]*/, float* sum_a /*[P] or NULL*/, float* sum_b /*[Q] or NULL*/,
+               float* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

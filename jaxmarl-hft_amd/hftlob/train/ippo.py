@@ -41,6 +41,10 @@ With ``GROUPED_SCAN`` (on top of ``FUSED_GRU``) the agent types' minibatch steps
 joint step whose sequence scans are one HIP launch per direction for all the types
 (``train.gru.gru_scan_grouped``): the nets and their data are independent, so every parameter, optimiser
 state and metric is bit for bit what the per-type steps give.
+With ``FUSED_WGRAD`` the weight and bias gradients of the narrow layers (``embed``, ``actor2``, ``critic2``) are
+two HIP launches each (``train.wgrad.narrow_linear``: a reduction split over the minibatch's rows) instead of
+rocBLAS GEMMs that run on a handful of workgroups; the forward, the data gradients and the square layers stay
+with rocBLAS, and parameters, ``state_dict`` and checkpoints are untouched.
 """
 from __future__ import annotations
 
@@ -58,6 +62,7 @@ from .gru import MAX_GROUPS, SUPPORTED_HIDDEN, gru_scan, gru_scan_grouped, gru_s
 from .loss import gae as gae_fused, ppo_loss_fused, ppo_loss_supported
 from .optim import MAX_TENSORS, adam_clip_step, adam_clip_supported, init_adam_state
 from .policy import MAX_ACTIONS, MAX_HEADS, MAX_OBS_DIM, SAMPLE, policy_step_multi_supported, policy_step_net
+from .wgrad import MAX_P, SUPPORTED_Q, narrow_linear, narrow_linear_supported
 
 
 def _per_type(v, n: int) -> list:
@@ -73,7 +78,7 @@ def default_config(**kw) -> Dict:
          "GAE_LAMBDA": [0.85, 0.9], "CLIP_EPS": 0.2, "ENT_COEF": [0.01, 0.01], "VF_COEF": [0.5, 0.5],
          "MAX_GRAD_NORM": [0.5, 0.5], "ANNEAL_LR": [True, True], "NUM_AGENTS_PER_TYPE": [1, 1], "SEED": 2,
          "CUDA_GRAPHS": True, "FUSED_GRU": False, "FUSED_POLICY": False, "FUSED_LOSS": False,
-         "FUSED_OPT": False, "GROUPED_SCAN": False, "CALC_EVAL": False,
+         "FUSED_OPT": False, "GROUPED_SCAN": False, "FUSED_WGRAD": False, "CALC_EVAL": False,
          "NUM_STEPS_EVAL": None}   # NUM_STEPS_EVAL None: NUM_STEPS
     c.update(kw)
     return c
@@ -112,6 +117,13 @@ class ActorCriticRNN(nn.Module):
                     blk.copy_(nn.init.orthogonal_(torch.empty_like(blk), 0.01))
         self.hidden = hidden
         self.fused = False   # forward's scan as one HIP launch per direction (train.gru.gru_scan); the trainer sets it
+        # the narrow layers' weight and bias gradients through train.wgrad.narrow_linear; the trainer sets it
+        self.fused_wgrad = False
+
+    def _linear(self, m: nn.Linear, x: torch.Tensor) -> torch.Tensor:
+        """A narrow layer of the sequence forward: the module itself, or with ``fused_wgrad`` the same
+        ``F.linear`` of its own weight and bias with the fused weight gradient behind it."""
+        return narrow_linear(x, m.weight, m.bias) if self.fused_wgrad else m(x)
 
     def action_shape(self, *lead: int) -> tuple:
         """The shape of the public action tensor of ``lead`` actors: one word each for a Discrete space,
@@ -146,11 +158,12 @@ class ActorCriticRNN(nn.Module):
     def gi_all(self, obs: torch.Tensor) -> torch.Tensor:
         """The input side of ``forward``: the embedding and the GRU's input projection over all T at once,
         [T, B, 3H] in gate order (r, z, n)."""
-        return F.linear(F.relu(self.embed(obs)), self.gru.weight_ih, self.gru.bias_ih)
+        return F.linear(F.relu(self._linear(self.embed, obs)), self.gru.weight_ih, self.gru.bias_ih)
 
     def head_outputs(self, hseq: torch.Tensor):
         """The heads of ``forward`` on the scan's hseq [T, B, H]: logits [T, B, A], values [T, B]."""
-        return self.actor2(F.relu(self.actor1(hseq))), self.critic2(F.relu(self.critic1(hseq))).squeeze(-1)
+        return (self._linear(self.actor2, F.relu(self.actor1(hseq))),
+                self._linear(self.critic2, F.relu(self.critic1(hseq))).squeeze(-1))
 
     def forward(self, h0: torch.Tensor, obs: torch.Tensor, dones: torch.Tensor):
         """A sequence [T, B, ...] from carry h0 (the ScannedRNN scan): logits [T, B, A], values [T, B].
@@ -342,6 +355,20 @@ class IPPOTrainer:
                 if not adam_clip_supported(len(list(n.parameters()))):
                     raise ValueError(f"FUSED_OPT needs <= {MAX_TENSORS} parameter tensors in a net, got "
                                      f"{len(list(n.parameters()))} (agent type {i})")
+        # FUSED_WGRAD: the weight and bias gradients of embed, actor2 and critic2 in the minibatch step as two HIP
+        # launches each (train.wgrad.narrow_linear; GPU only, and there is no other path behind the switch)
+        self.fused_wgrad = bool(c.get("FUSED_WGRAD", False))
+        if self.fused_wgrad:
+            if self.device.type != "cuda":
+                raise ValueError(f"FUSED_WGRAD needs a GPU device, got {self.device}")
+            for i, n in enumerate(self.nets):
+                for m in (n.embed, n.actor2, n.critic2):
+                    if not narrow_linear_supported(m.in_features, m.out_features):
+                        raise ValueError(f"FUSED_WGRAD needs GRU_HIDDEN_DIM and FC_DIM_SIZE in {list(SUPPORTED_Q)}, an "
+                                         f"observation size <= {MAX_P} and <= {MAX_P} actions over all heads, got "
+                                         f"{c['GRU_HIDDEN_DIM']}, {c['FC_DIM_SIZE']}, {n.embed.in_features} and "
+                                         f"{sum(n.heads)} (agent type {i})")
+                n.fused_wgrad = True
         # CALC_EVAL (:461-482, 876-975): after every update NUM_STEPS_EVAL sampled steps of the current nets
         # in a separate eval env, through the fused policy step and the tally launch (evaluate_policy)
         self.calc_eval = bool(c.get("CALC_EVAL", False))
@@ -773,7 +800,7 @@ def train(env: MARLEnv, config: Dict, n_updates: Optional[int] = None, dist=None
 
 def main(argv=None) -> None:
     """python -m hftlob.train.ippo [--rl-config ippo.yaml] [--env-config 2_player_fq_fqc] [--updates N]
-    [--fused-gru] [--fused-policy] [--fused-loss] [--fused-opt] [--grouped-scan]"""
+    [--fused-gru] [--fused-policy] [--fused-loss] [--fused-opt] [--grouped-scan] [--fused-wgrad]"""
     import argparse
     import json
     import yaml
@@ -793,6 +820,9 @@ def main(argv=None) -> None:
     ap.add_argument("--grouped-scan", action="store_true",
                     help="the agent types' minibatch steps in lockstep, their GRU scans one HIP launch per direction "
                          "(needs --fused-gru)")
+    ap.add_argument("--fused-wgrad", action="store_true",
+                    help="the narrow layers' (embed, actor2, critic2) weight and bias gradients as two fused HIP "
+                         "launches each")
     ap.add_argument("--calc-eval", action="store_true",
                     help="CALC_EVAL: after every update NUM_STEPS_EVAL sampled steps in a separate eval env (the same "
                          "config, a synthetic day of another seed), logged as avg_reward_eval")
@@ -815,6 +845,8 @@ def main(argv=None) -> None:
         c["FUSED_OPT"] = True
     if a.grouped_scan:
         c["GROUPED_SCAN"] = True
+    if a.fused_wgrad:
+        c["FUSED_WGRAD"] = True
     if a.calc_eval:
         c["CALC_EVAL"] = True
     cfg = (load_config_from_file(a.env_config) if a.env_config.endswith((".json", ".yaml"))

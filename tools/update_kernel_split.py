@@ -9,7 +9,8 @@
 A minibatch step is the run of kernels that ends with k_adam_update; steps whose window also holds a
 rollout, GAE or env kernel are left out.  The steps are grouped by their kernel count (the two agent
 types differ by one kernel) and the two commonest groups are summarised: kernel time per step by bucket
-(scan forward / backward, rocBLAS GEMMs, gathers and copies, loss, optimiser step, rest) and by kernel
+(scan forward / backward, the narrow layers' weight gradients with --fused-wgrad, rocBLAS GEMMs, gathers and
+copies, loss, optimiser step, rest) and by kernel
 name, and the window from the step's first start to its last end.
 
 With --grouped-scan in the traced command the same rule cuts a joint step of all agent types in two: the
@@ -31,6 +32,7 @@ rows.sort()
 def bucket(n):
     if "k_gru_scan_fwd" in n: return "scan forward"
     if "k_gru_scan_bwd" in n: return "scan backward"
+    if "k_xty" in n: return "narrow weight gradients"
     if n.startswith("Cijk_") or "gemm" in n.lower() or "rocblas" in n.lower() or "gemv" in n.lower(): return "rocBLAS GEMMs"
     if "k_moments" in n or "k_loss" in n or "k_final" in n: return "loss"
     if "k_adam" in n: return "optimiser step"
@@ -66,7 +68,7 @@ with open(out, "w") as o:
         allk = sum(tot.values()) / k
         P(f"sum of kernel times per step: {allk:.1f} us")
         for b in sorted(tot, key=lambda b: -tot[b]):
-            P(f"  {b:20s} {tot[b] / k:9.1f} us  {100 * tot[b] / k / allk:5.1f} %  {num[b] / k:6.1f} kernels")
+            P(f"  {b:24s} {tot[b] / k:9.1f} us  {100 * tot[b] / k / allk:5.1f} %  {num[b] / k:6.1f} kernels")
         P("by kernel name (us per step, launches per step):")
         for (b, n), t in sorted(byname.items(), key=lambda x: -x[1])[:45]:
             P(f"  {t / k:9.2f} {nname[(b, n)] / k:6.1f}  [{b}] {n[:110]}")
