@@ -819,6 +819,57 @@ int hftlob_xty(long long N, int P, int Q, const float* A /*[N][P]*/, const float
                float* C /*[P][Q]*/, float* sum_a /*[P] or NULL*/, float* sum_b /*[Q] or NULL*/,
                float* workspace, void* stream);
 
+/* The weight and bias gradients of the learner's wide layers: the same product for a wide output, float32,
+ *       C[P][Q]  = sum_n A[n][p] B'[n][q]         row-major, contiguous
+ *       sum_a[P] = sum_n A[n][p]                  (NULL to skip)
+ * for P a multiple of 64 in 64..HFTLOB_XTY_WIDE_MAX_P, Q 64, 128 or 256, N >= 0.  For a linear layer y = x W^T
+ * + b (W [P][Q]) A = d_y, B = x give d_W = C and d_b = sum_a.
+ *   A is one or two column blocks side by side, P = cols0 + cols1: block i is (Ai, colsi, stridei), row n of
+ *     it the colsi floats at Ai + n stridei.  colsi is a multiple of 64 (cols1 = 0: one block, A1 is not
+ *     looked at), stridei >= colsi and a multiple of 4, Ai 16-byte aligned.
+ *   B' is B [N][Q] (contiguous, 16-byte aligned) behind a head and under a row mask:
+ *         B'[n] = zero_row[n] ? 0 : (n < shift ? head[n] : B[n - shift])
+ *     head is [shift][Q] (16-byte aligned; NULL: those rows are 0), zero_row N bytes (NULL: no mask), 0 <=
+ *     shift <= N.  Rows N - shift .. of B are never read, nor is a masked row's value used (it may be NaN).
+ *     With shift = the batch size, head = h0, B = hseq and zero_row = done, B' is the h_prev of
+ *     hftlob_gru_scan_bwd's W_hh gradient, and A = (d_gi with cols 2H and stride 3H, d_gh_n) its d_gh.
+ * Two launches on the caller's stream:
+ *   the partial pass cuts the rows into G contiguous stripes and C into tiles of HFTLOB_XTY_WIDE_TILE_P rows
+ *     by TQ columns, TQ = 64 for Q = 64 and 128 otherwise; one workgroup per stripe and tile.  The stripe
+ *     rule is a function of (N, P, Q), with R = HFTLOB_XTY_WIDE_STRIPE_ROWS, tiles = ceil(P / 128) (Q / TQ)
+ *     and M = ceil(HFTLOB_XTY_WIDE_TARGET_WGS / tiles):
+ *         rows = R if ceil(N / R) <= M, else ceil(N / M)        G = ceil(N / rows)
+ *     stripe g is the rows [g rows, min(N, (g + 1) rows)): up to M stripes of R rows, and past M R rows the
+ *     stripes grow instead of their number; none is empty.  A workgroup walks its stripe in chunks of
+ *     HFTLOB_XTY_WIDE_CHUNK rows and adds a[p] b[q] in row order with float32 matrix instructions whose
+ *     result is that of one fused multiply-add (fmaf) per row; sum_a's partial is a float32 sum in row order.
+ *     It leaves its float32 partial in the workspace: per stripe P Q + P floats, [P][Q] of C, then sum_a's
+ *     (only when asked for);
+ *   the final pass adds the G partials of every output element in double, in stripe order, and rounds once
+ *     to float32.
+ * No floating-point atomic and a fixed order of every sum: the same inputs give the same bits on every
+ * call, eager or replayed from a HIP graph, and C's bits do not depend on whether sum_a is asked for, nor on
+ * how A is cut into blocks or whether B' is given shifted and masked or materialised.  Rows past N are
+ * never read.  workspace is the caller's, hftlob_xty_wide_workspace(N, P, Q) floats (G (P Q + P); a host-only
+ * function that makes no device call), written before it is read.  N = 0 zero-fills C and sum_a (if not NULL)
+ * with asynchronous memsets and reads nothing: every other pointer may then be NULL.  The call neither
+ * allocates nor synchronises and can be captured in a HIP graph.  Checked in this order, before any device
+ * work: HFTLOB_ESHAPE: cols0 not a multiple of 64 in 64..768, cols1 not 0 or such a multiple, P > 768, Q not
+ * 64, 128 or 256, N < 0 (hftlob_xty_wide_workspace returns the same code for its P, Q and N, as a negative
+ * size), shift outside 0..N; HFTLOB_ENULL: a NULL C, or with N > 0 a NULL A0, A1 (cols1 > 0), B (shift < N) or workspace;
+ * HFTLOB_EINVAL: with N > 0 an A0, A1, B or head that is not 16-byte aligned, then a stride below its block's
+ * columns or not a multiple of 4. */
+#define HFTLOB_XTY_WIDE_MAX_P 768
+#define HFTLOB_XTY_WIDE_TILE_P 128        /* rows of C in a workgroup's tile */
+#define HFTLOB_XTY_WIDE_CHUNK 32          /* rows of A and B in a chunk */
+#define HFTLOB_XTY_WIDE_STRIPE_ROWS 256   /* R: the rows of a stripe up to M stripes */
+#define HFTLOB_XTY_WIDE_TARGET_WGS 512    /* M tiles >= this: two workgroups on each of 256 CUs */
+long long hftlob_xty_wide_workspace(long long N, int P, int Q);   /* floats; < 0: an error code */
+int hftlob_xty_wide(long long N, int Q, const float* A0, int cols0, long long stride0, const float* A1, int cols1,
+                    long long stride1, const float* B /*[N][Q]*/, const float* head /*[shift][Q] or NULL*/,
+                    long long shift, const unsigned char* zero_row /*[N] or NULL*/, float* C /*[P][Q]*/,
+                    float* sum_a /*[P] or NULL*/, float* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

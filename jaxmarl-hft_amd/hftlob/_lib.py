@@ -53,7 +53,7 @@ EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob
            "hftlob_sample_actions", "hftlob_split_keys", "hftlob_gru_scan_fwd", "hftlob_gru_scan_bwd",
            "hftlob_gru_scan_fwd_grouped", "hftlob_gru_scan_bwd_grouped",
            "hftlob_policy_step", "hftlob_policy_step_multi", "hftlob_gae", "hftlob_ppo_loss",
-           "hftlob_adam_clip", "hftlob_xty", "hftlob_xty_workspace")
+           "hftlob_adam_clip", "hftlob_xty", "hftlob_xty_workspace", "hftlob_xty_wide", "hftlob_xty_wide_workspace")
 
 _lib = None
 
@@ -140,6 +140,11 @@ def lib() -> C.CDLL:
     L.hftlob_xty.restype = i32
     L.hftlob_xty_workspace.argtypes = [C.c_longlong, i32, i32]
     L.hftlob_xty_workspace.restype = C.c_longlong
+    L.hftlob_xty_wide.argtypes = [C.c_longlong, i32, vp, i32, C.c_longlong, vp, i32, C.c_longlong, vp, vp, C.c_longlong,
+                                  vp, vp, vp, vp, vp]
+    L.hftlob_xty_wide.restype = i32
+    L.hftlob_xty_wide_workspace.argtypes = [C.c_longlong, i32, i32]
+    L.hftlob_xty_wide_workspace.restype = C.c_longlong
     if L.hftlob_version() != ABI_VERSION:
         raise RuntimeError(f"libhftlob ABI {L.hftlob_version()} != {ABI_VERSION}")
     _lib = L

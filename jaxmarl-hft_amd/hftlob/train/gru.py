@@ -9,7 +9,8 @@ every group's results bit for bit those of ``gru_scan`` on that group alone.
 ``hftlob_gru_scan_bwd`` (include/hftlob.h) in torch, in whatever float type they are given: they
 are the spec of the kernels and what the tests compare against.  ``gru_scan`` is the fused path:
 one HIP launch per direction, the weight and bias gradients formed by torch as one GEMM and one
-reduction over all T.
+reduction over all T (``weight_grads``), or with ``fused_wgrad`` by ``weight_grads_fused``: one
+``hftlob_xty_wide`` call that reads d_gi, d_gh_n, hseq, h0 and done where they lie.
 
 Notation: ``gi`` [T, B, 3H] is the input projection in gate order (r, z, n), ``done`` [T, B]
 resets the carry entering step t, ``h_prev(t) = done[t] ? 0 : (t ? hseq[t-1] : h0)``, and
@@ -20,6 +21,7 @@ from __future__ import annotations
 import torch
 
 from .. import _lib
+from .wgrad import aligned, xty_wide
 
 SUPPORTED_HIDDEN = (64, 128, 256)   # the kernels' template instantiations (csrc/gru_scan.hip)
 MAX_GROUPS = 8                      # HFTLOB_GRU_MAX_GROUPS: sequence batches in one grouped launch
@@ -85,6 +87,22 @@ def weight_grads(d_gi, d_gh_n, hseq, h0, done):
     return d_gh.t() @ _h_prev(hseq, h0, done).reshape(-1, H), d_gh.sum(0)
 
 
+def fused_wgrad_operands(d_gi, d_gh_n, hseq, h0, done):
+    """``weight_grads`` as the operands of ``wgrad.xty_wide`` / ``xty_wide_reference`` (a_blocks, B, head,
+    shift, zero_row), all of them views: d_gh is the first 2H columns of d_gi beside d_gh_n, and h_prev is
+    hseq one step (B rows) late behind h0, zeroed where done."""
+    T, B, H = hseq.shape
+    return ([d_gi.reshape(T * B, 3 * H)[:, :2 * H], d_gh_n.reshape(T * B, H)], hseq.reshape(T * B, H), h0, B,
+            done.reshape(T * B))
+
+
+def weight_grads_fused(d_gi, d_gh_n, hseq, h0, done):
+    """(d_w_hh [3H, H], d_b_hh [3H]) as one ``hftlob_xty_wide`` call on contiguous float32 device tensors:
+    ``weight_grads`` without its two concatenations and its select."""
+    blocks, rows, head, shift, zero_row = fused_wgrad_operands(d_gi, d_gh_n, hseq, h0, done)
+    return xty_wide([aligned(a) for a in blocks], aligned(rows), aligned(head), shift, zero_row, want_sum_a=True)
+
+
 def _f32(t):
     return t.detach().to(torch.float32).contiguous()
 
@@ -133,9 +151,10 @@ class GRUScan(torch.autograd.Function):
     """hseq = gru_scan(gi, h0, done, w_hh, b_hh), differentiable in gi, h0, w_hh and b_hh."""
 
     @staticmethod
-    def forward(ctx, gi, h0, done, w_hh, b_hh):
+    def forward(ctx, gi, h0, done, w_hh, b_hh, fused_wgrad=False):
         need = any(ctx.needs_input_grad)
         hseq, gates = scan_forward(gi, h0, done, w_hh, b_hh, save_gates=need)
+        ctx.fused_wgrad = bool(fused_wgrad)
         if need:
             ctx.save_for_backward(hseq, gates, _f32(h0), done, _f32(w_hh))
         return hseq
@@ -147,13 +166,14 @@ class GRUScan(torch.autograd.Function):
         d_gi, d_gh_n, d_h0 = scan_backward(d_hseq, hseq, gates, h0, done, w_hh)
         d_w, d_b = (None, None)
         if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
-            d_w, d_b = weight_grads(d_gi, d_gh_n, hseq, h0, done)
-        return d_gi, d_h0, None, d_w, d_b
+            d_w, d_b = (weight_grads_fused if ctx.fused_wgrad else weight_grads)(d_gi, d_gh_n, hseq, h0, done)
+        return d_gi, d_h0, None, d_w, d_b, None
 
 
-def gru_scan(gi, h0, done, w_hh, b_hh):
-    """The fused scan: hseq [T, B, H] (float32, on the device of ``gi``)."""
-    return GRUScan.apply(gi, h0, done, w_hh, b_hh)
+def gru_scan(gi, h0, done, w_hh, b_hh, fused_wgrad: bool = False):
+    """The fused scan: hseq [T, B, H] (float32, on the device of ``gi``).  With ``fused_wgrad`` the backward
+    forms W_hh's and b_hh's gradients with ``weight_grads_fused`` instead of ``weight_grads``."""
+    return GRUScan.apply(gi, h0, done, w_hh, b_hh, fused_wgrad)
 
 
 def _check_groups(what: str, shapes) -> tuple:
@@ -230,10 +250,11 @@ class GRUScanGrouped(torch.autograd.Function):
     done, the n w_hh and the n b_hh.  Every group is differentiable in its gi, h0, w_hh and b_hh."""
 
     @staticmethod
-    def forward(ctx, n, *flat):
+    def forward(ctx, n, fused_wgrad, *flat):
         gis, h0s, dones, w_hhs, b_hhs = (flat[k * n:(k + 1) * n] for k in range(5))
-        # (needs_input_grad[0] is n's)
-        need = [any(ctx.needs_input_grad[1 + k * n + g] for k in (0, 1, 3, 4)) for g in range(n)]
+        ctx.fused_wgrad = bool(fused_wgrad)
+        # (needs_input_grad[0] and [1] are n's and fused_wgrad's)
+        need = [any(ctx.needs_input_grad[2 + k * n + g] for k in (0, 1, 3, 4)) for g in range(n)]
         out = scan_forward_grouped(list(zip(gis, h0s, dones, w_hhs, b_hhs)), save_gates=need)
         ctx.n, ctx.need = n, need
         saved = []
@@ -256,15 +277,17 @@ class GRUScanGrouped(torch.autograd.Function):
             for g, (d_gi, d_gh_n, d_h0) in zip(live, res):
                 hseq, _, h0, done, _ = per[g]
                 grads[g], grads[n + g] = d_gi, d_h0
-                if ctx.needs_input_grad[1 + 3 * n + g] or ctx.needs_input_grad[1 + 4 * n + g]:
-                    grads[3 * n + g], grads[4 * n + g] = weight_grads(d_gi, d_gh_n, hseq, h0, done)
-        return (None, *grads)
+                if ctx.needs_input_grad[2 + 3 * n + g] or ctx.needs_input_grad[2 + 4 * n + g]:
+                    wg = weight_grads_fused if ctx.fused_wgrad else weight_grads
+                    grads[3 * n + g], grads[4 * n + g] = wg(d_gi, d_gh_n, hseq, h0, done)
+        return (None, None, *grads)
 
 
-def gru_scan_grouped(gis, h0s, dones, w_hhs, b_hhs):
+def gru_scan_grouped(gis, h0s, dones, w_hhs, b_hhs, fused_wgrad: bool = False):
     """The fused scans of several independent nets as one launch per direction: a tuple of hseq [T, B_g, H],
-    group g's equal bit for bit to ``gru_scan(gis[g], h0s[g], dones[g], w_hhs[g], b_hhs[g])``, and so are
-    its gradients (the weight and bias gradients are ``weight_grads`` per group)."""
+    group g's equal bit for bit to ``gru_scan(gis[g], h0s[g], dones[g], w_hhs[g], b_hhs[g], fused_wgrad)``,
+    and so are its gradients (the weight and bias gradients are ``weight_grads`` per group, or with
+    ``fused_wgrad`` ``weight_grads_fused``)."""
     lists = [list(x) for x in (gis, h0s, dones, w_hhs, b_hhs)]
     n = len(lists[0])
     if any(len(x) != n for x in lists):
@@ -274,4 +297,4 @@ def gru_scan_grouped(gis, h0s, dones, w_hhs, b_hhs):
         if gi.dim() != 3 or gi.shape[2] % 3:
             raise ValueError("gru_scan_grouped: gi must be [T, B, 3H]")
     _check_groups("gru_scan_grouped", [(gi.shape[0], gi.shape[1], gi.shape[2] // 3) for gi in lists[0]])
-    return GRUScanGrouped.apply(n, *(t for x in lists for t in x))
+    return GRUScanGrouped.apply(n, bool(fused_wgrad), *(t for x in lists for t in x))

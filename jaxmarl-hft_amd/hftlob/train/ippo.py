@@ -45,6 +45,10 @@ With ``FUSED_WGRAD`` the weight and bias gradients of the narrow layers (``embed
 two HIP launches each (``train.wgrad.narrow_linear``: a reduction split over the minibatch's rows) instead of
 rocBLAS GEMMs that run on a handful of workgroups; the forward, the data gradients and the square layers stay
 with rocBLAS, and parameters, ``state_dict`` and checkpoints are untouched.
+``FUSED_WGRAD_WIDE`` does the same, independently, for the wide layers (the GRU's ``weight_ih``, ``actor1``,
+``critic1``: ``train.wgrad.wide_linear``, the product on the matrix cores), and with ``FUSED_GRU`` for the
+GRU's ``weight_hh`` (``train.gru.weight_grads_fused``, which also drops the concatenations and the select that
+built its operands).
 """
 from __future__ import annotations
 
@@ -62,7 +66,7 @@ from .gru import MAX_GROUPS, SUPPORTED_HIDDEN, gru_scan, gru_scan_grouped, gru_s
 from .loss import gae as gae_fused, ppo_loss_fused, ppo_loss_supported
 from .optim import MAX_TENSORS, adam_clip_step, adam_clip_supported, init_adam_state
 from .policy import MAX_ACTIONS, MAX_HEADS, MAX_OBS_DIM, SAMPLE, policy_step_multi_supported, policy_step_net
-from .wgrad import MAX_P, SUPPORTED_Q, narrow_linear, narrow_linear_supported
+from .wgrad import MAX_P, SUPPORTED_Q, narrow_linear, narrow_linear_supported, wide_linear, wide_linear_supported
 
 
 def _per_type(v, n: int) -> list:
@@ -78,7 +82,7 @@ def default_config(**kw) -> Dict:
          "GAE_LAMBDA": [0.85, 0.9], "CLIP_EPS": 0.2, "ENT_COEF": [0.01, 0.01], "VF_COEF": [0.5, 0.5],
          "MAX_GRAD_NORM": [0.5, 0.5], "ANNEAL_LR": [True, True], "NUM_AGENTS_PER_TYPE": [1, 1], "SEED": 2,
          "CUDA_GRAPHS": True, "FUSED_GRU": False, "FUSED_POLICY": False, "FUSED_LOSS": False,
-         "FUSED_OPT": False, "GROUPED_SCAN": False, "FUSED_WGRAD": False, "CALC_EVAL": False,
+         "FUSED_OPT": False, "GROUPED_SCAN": False, "FUSED_WGRAD": False, "FUSED_WGRAD_WIDE": False, "CALC_EVAL": False,
          "NUM_STEPS_EVAL": None}   # NUM_STEPS_EVAL None: NUM_STEPS
     c.update(kw)
     return c
@@ -119,6 +123,14 @@ class ActorCriticRNN(nn.Module):
         self.fused = False   # forward's scan as one HIP launch per direction (train.gru.gru_scan); the trainer sets it
         # the narrow layers' weight and bias gradients through train.wgrad.narrow_linear; the trainer sets it
         self.fused_wgrad = False
+        # the wide layers' (gru.weight_ih, actor1, critic1, and with ``fused`` gru.weight_hh) weight and bias
+        # gradients through train.wgrad.wide_linear and train.gru.weight_grads_fused; the trainer sets it
+        self.fused_wgrad_wide = False
+
+    def _wide(self, x: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        """A wide layer of the sequence forward: ``F.linear``, with ``fused_wgrad_wide`` the fused weight
+        gradient behind it."""
+        return wide_linear(x, w, b) if self.fused_wgrad_wide else F.linear(x, w, b)
 
     def _linear(self, m: nn.Linear, x: torch.Tensor) -> torch.Tensor:
         """A narrow layer of the sequence forward: the module itself, or with ``fused_wgrad`` the same
@@ -158,20 +170,23 @@ class ActorCriticRNN(nn.Module):
     def gi_all(self, obs: torch.Tensor) -> torch.Tensor:
         """The input side of ``forward``: the embedding and the GRU's input projection over all T at once,
         [T, B, 3H] in gate order (r, z, n)."""
-        return F.linear(F.relu(self._linear(self.embed, obs)), self.gru.weight_ih, self.gru.bias_ih)
+        return self._wide(F.relu(self._linear(self.embed, obs)), self.gru.weight_ih, self.gru.bias_ih)
 
     def head_outputs(self, hseq: torch.Tensor):
         """The heads of ``forward`` on the scan's hseq [T, B, H]: logits [T, B, A], values [T, B]."""
-        return (self._linear(self.actor2, F.relu(self.actor1(hseq))),
-                self._linear(self.critic2, F.relu(self.critic1(hseq))).squeeze(-1))
+        a1 = self._wide(hseq, self.actor1.weight, self.actor1.bias)
+        c1 = self._wide(hseq, self.critic1.weight, self.critic1.bias)
+        return self._linear(self.actor2, F.relu(a1)), self._linear(self.critic2, F.relu(c1)).squeeze(-1)
 
     def forward(self, h0: torch.Tensor, obs: torch.Tensor, dones: torch.Tensor):
         """A sequence [T, B, ...] from carry h0 (the ScannedRNN scan): logits [T, B, A], values [T, B].
         The same cell as ``step``; the input-side GEMMs (embedding, the GRU's input
         projection, both heads) run once over all T, only h @ W_hh stays in the scan: the loop
         of ``scan_loop``, or with ``fused`` set one HIP launch forward and one backward."""
-        scan = gru_scan if self.fused else self.scan_loop
-        hseq = scan(self.gi_all(obs), h0, dones, self.gru.weight_hh, self.gru.bias_hh)
+        if self.fused:
+            hseq = gru_scan(self.gi_all(obs), h0, dones, self.gru.weight_hh, self.gru.bias_hh, self.fused_wgrad_wide)
+        else:
+            hseq = self.scan_loop(self.gi_all(obs), h0, dones, self.gru.weight_hh, self.gru.bias_hh)
         return self.head_outputs(hseq)
 
     @staticmethod
@@ -183,7 +198,8 @@ class ActorCriticRNN(nn.Module):
         gis = [net.gi_all(obs) for net, obs in zip(nets, obss)]
         if all(net.fused for net in nets):
             hseqs = gru_scan_grouped(gis, h0s, dones, [net.gru.weight_hh for net in nets],
-                                     [net.gru.bias_hh for net in nets])
+                                     [net.gru.bias_hh for net in nets],
+                                     fused_wgrad=all(net.fused_wgrad_wide for net in nets))
         else:
             hseqs = [net.scan_loop(gi, h0, d, net.gru.weight_hh, net.gru.bias_hh)
                      for net, gi, h0, d in zip(nets, gis, h0s, dones)]
@@ -369,6 +385,21 @@ class IPPOTrainer:
                                          f"{c['GRU_HIDDEN_DIM']}, {c['FC_DIM_SIZE']}, {n.embed.in_features} and "
                                          f"{sum(n.heads)} (agent type {i})")
                 n.fused_wgrad = True
+        # FUSED_WGRAD_WIDE: the weight and bias gradients of gru.weight_ih, actor1 and critic1, and with the fused
+        # scan of gru.weight_hh, as two HIP launches each (train.wgrad.wide_linear, train.gru.weight_grads_fused;
+        # GPU only, and there is no other path behind the switch)
+        self.fused_wgrad_wide = bool(c.get("FUSED_WGRAD_WIDE", False))
+        if self.fused_wgrad_wide:
+            if self.device.type != "cuda":
+                raise ValueError(f"FUSED_WGRAD_WIDE needs a GPU device, got {self.device}")
+            for i, n in enumerate(self.nets):
+                for in_f, out_f in ((n.gru.input_size, 3 * n.hidden), (n.hidden, 3 * n.hidden),
+                                    (n.actor1.in_features, n.actor1.out_features),
+                                    (n.critic1.in_features, n.critic1.out_features)):
+                    if not wide_linear_supported(in_f, out_f):
+                        raise ValueError(f"FUSED_WGRAD_WIDE needs GRU_HIDDEN_DIM and FC_DIM_SIZE in {list(SUPPORTED_Q)}, "
+                                         f"got {c['GRU_HIDDEN_DIM']} and {c['FC_DIM_SIZE']} (agent type {i})")
+                n.fused_wgrad_wide = True
         # CALC_EVAL (:461-482, 876-975): after every update NUM_STEPS_EVAL sampled steps of the current nets
         # in a separate eval env, through the fused policy step and the tally launch (evaluate_policy)
         self.calc_eval = bool(c.get("CALC_EVAL", False))
@@ -800,7 +831,8 @@ def train(env: MARLEnv, config: Dict, n_updates: Optional[int] = None, dist=None
 
 def main(argv=None) -> None:
     """python -m hftlob.train.ippo [--rl-config ippo.yaml] [--env-config 2_player_fq_fqc] [--updates N]
-    [--fused-gru] [--fused-policy] [--fused-loss] [--fused-opt] [--grouped-scan] [--fused-wgrad]"""
+    [--fused-gru] [--fused-policy] [--fused-loss] [--fused-opt] [--grouped-scan] [--fused-wgrad]
+    [--fused-wgrad-wide]"""
     import argparse
     import json
     import yaml
@@ -823,6 +855,9 @@ def main(argv=None) -> None:
     ap.add_argument("--fused-wgrad", action="store_true",
                     help="the narrow layers' (embed, actor2, critic2) weight and bias gradients as two fused HIP "
                          "launches each")
+    ap.add_argument("--fused-wgrad-wide", action="store_true",
+                    help="the wide layers' (the GRU's two weight matrices, actor1, critic1) weight and bias gradients "
+                         "as two fused HIP launches each")
     ap.add_argument("--calc-eval", action="store_true",
                     help="CALC_EVAL: after every update NUM_STEPS_EVAL sampled steps in a separate eval env (the same "
                          "config, a synthetic day of another seed), logged as avg_reward_eval")
@@ -847,6 +882,8 @@ def main(argv=None) -> None:
         c["GROUPED_SCAN"] = True
     if a.fused_wgrad:
         c["FUSED_WGRAD"] = True
+    if a.fused_wgrad_wide:
+        c["FUSED_WGRAD_WIDE"] = True
     if a.calc_eval:
         c["CALC_EVAL"] = True
     cfg = (load_config_from_file(a.env_config) if a.env_config.endswith((".json", ".yaml"))

@@ -1,7 +1,7 @@
 """Time the IPPO learner's phases on the GPU (rollout vs PPO epochs) at the metric config.
 
     python tools/train_timing.py [--graph] [--fused-gru] [--fused-policy] [--fused-loss] [--fused-opt] [--grouped-scan]
-                                   [--fused-wgrad] [--updates N]
+                                   [--fused-wgrad] [--fused-wgrad-wide] [--updates N]
 
 --graph: CUDA_GRAPHS (the rollout and each minibatch step replayed as HIP graphs);
 --fused-gru: FUSED_GRU (the minibatch step's GRU scan through hftlob_gru_scan_fwd / _bwd);
@@ -12,6 +12,7 @@ hftlob_ppo_loss);
 --grouped-scan: GROUPED_SCAN (the agent types' minibatch steps in lockstep, their scans through
 hftlob_gru_scan_fwd_grouped / _bwd_grouped; needs --fused-gru);
 --fused-wgrad: FUSED_WGRAD (the narrow layers' weight and bias gradients through hftlob_xty);
+--fused-wgrad-wide: FUSED_WGRAD_WIDE (the wide layers' weight and bias gradients through hftlob_xty_wide);
 --updates N: the timed rollout + update rounds after the first, untimed update (default 3)."""
 import os
 import sys
@@ -37,7 +38,7 @@ def main():
     c = I.default_config(NUM_ENVS=4096, NUM_STEPS=64, TOTAL_TIMESTEPS=4096 * 64 * 50, CUDA_GRAPHS=graph,
                          FUSED_GRU="--fused-gru" in sys.argv, FUSED_POLICY="--fused-policy" in sys.argv,
                          FUSED_LOSS="--fused-loss" in sys.argv, FUSED_OPT="--fused-opt" in sys.argv,
-                         FUSED_WGRAD="--fused-wgrad" in sys.argv,
+                         FUSED_WGRAD="--fused-wgrad" in sys.argv, FUSED_WGRAD_WIDE="--fused-wgrad-wide" in sys.argv,
                          **({"GROUPED_SCAN": True} if "--grouped-scan" in sys.argv else {}))
     rounds = int(sys.argv[sys.argv.index("--updates") + 1]) if "--updates" in sys.argv else 3
     tr = I.IPPOTrainer(env, c)

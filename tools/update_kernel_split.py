@@ -9,8 +9,8 @@
 A minibatch step is the run of kernels that ends with k_adam_update; steps whose window also holds a
 rollout, GAE or env kernel are left out.  The steps are grouped by their kernel count (the two agent
 types differ by one kernel) and the two commonest groups are summarised: kernel time per step by bucket
-(scan forward / backward, the narrow layers' weight gradients with --fused-wgrad, rocBLAS GEMMs, gathers and
-copies, loss, optimiser step, rest) and by kernel
+(scan forward / backward, the narrow layers' weight gradients with --fused-wgrad, the wide layers' with
+--fused-wgrad-wide, rocBLAS GEMMs, gathers and copies, loss, optimiser step, rest) and by kernel
 name, and the window from the step's first start to its last end.
 
 With --grouped-scan in the traced command the same rule cuts a joint step of all agent types in two: the
@@ -32,6 +32,7 @@ rows.sort()
 def bucket(n):
     if "k_gru_scan_fwd" in n: return "scan forward"
     if "k_gru_scan_bwd" in n: return "scan backward"
+    if "k_xtyw" in n: return "wide weight gradients"
     if "k_xty" in n: return "narrow weight gradients"
     if n.startswith("Cijk_") or "gemm" in n.lower() or "rocblas" in n.lower() or "gemv" in n.lower(): return "rocBLAS GEMMs"
     if "k_moments" in n or "k_loss" in n or "k_final" in n: return "loss"
