@@ -113,38 +113,51 @@ def _u8(done):
     return done.view(torch.uint8) if done.dtype == torch.bool else done.to(torch.uint8)
 
 
-def scan_forward(gi, h0, done, w_hh, b_hh, save_gates: bool = True):
-    """hftlob_gru_scan_fwd on device tensors: (hseq, gates or None)."""
+def _fwd_group(name: str, group, save_gates: bool):
+    """One group (gi, h0, done, w_hh, b_hh) of a forward launch as the operators take it: the converted
+    tensors (they must live until the launch is made), the pointers of those and of the two outputs in the
+    operators' argument order, and (hseq, gates or None).  ``name`` heads the shape error."""
+    gi, h0, done, w_hh, b_hh = group
     T, B, H3 = gi.shape
     H = H3 // 3
-    gi, h0, w_hh, b_hh = _f32(gi), _f32(h0), _f32(w_hh), _f32(b_hh)
-    done = _u8(done)
-    ptrs = [_lib.ptr(x) for x in (gi, h0, done, w_hh, b_hh)]   # (a CPU tensor raises here)
+    keep = gi, h0, done, w_hh, b_hh = _f32(gi), _f32(h0), _u8(done), _f32(w_hh), _f32(b_hh)
     if h0.shape != (B, H) or done.shape != (T, B) or w_hh.shape != (3 * H, H) or b_hh.shape != (3 * H,):
-        raise ValueError(f"gru_scan: shapes gi {tuple(gi.shape)}, h0 {tuple(h0.shape)}, done {tuple(done.shape)}, "
+        raise ValueError(f"{name}: shapes gi {tuple(gi.shape)}, h0 {tuple(h0.shape)}, done {tuple(done.shape)}, "
                          f"w_hh {tuple(w_hh.shape)}, b_hh {tuple(b_hh.shape)} do not agree")
     hseq = torch.empty((T, B, H), dtype=torch.float32, device=gi.device)
     gates = torch.empty((T, B, 4 * H), dtype=torch.float32, device=gi.device) if save_gates else None
-    _lib.check(_lib.lib().hftlob_gru_scan_fwd(T, B, H, *ptrs, _lib.ptr(hseq), _lib.ptr(gates),
-                                              _lib.stream_ptr(device=gi.device)))
-    return hseq, gates
+    return keep, [_lib.ptr(x) for x in keep + (hseq, gates)], (hseq, gates)   # (a CPU tensor raises here)
+
+
+def _bwd_group(name: str, group):
+    """``_fwd_group`` for a backward launch: one group (d_hseq, hseq, gates, h0, done, w_hh), the outputs
+    (d_gi, d_gh_n, d_h0)."""
+    d_hseq, hseq, gates, h0, done, w_hh = group
+    T, B, H = hseq.shape
+    keep = d_hseq, hseq, gates, h0, done, w_hh = _f32(d_hseq), _f32(hseq), _f32(gates), _f32(h0), _u8(done), _f32(w_hh)
+    if d_hseq.shape != (T, B, H) or gates.shape != (T, B, 4 * H) or h0.shape != (B, H) or done.shape != (T, B) \
+            or w_hh.shape != (3 * H, H):
+        raise ValueError(f"{name}: shapes do not agree")
+    out = (torch.empty((T, B, 3 * H), dtype=torch.float32, device=hseq.device),
+           torch.empty((T, B, H), dtype=torch.float32, device=hseq.device),
+           torch.empty((B, H), dtype=torch.float32, device=hseq.device))
+    return keep, [_lib.ptr(x) for x in keep + out], out
+
+
+def scan_forward(gi, h0, done, w_hh, b_hh, save_gates: bool = True):
+    """hftlob_gru_scan_fwd on device tensors: (hseq, gates or None)."""
+    keep, ptrs, out = _fwd_group("gru_scan", (gi, h0, done, w_hh, b_hh), save_gates)
+    T, B, H = out[0].shape
+    _lib.check(_lib.lib().hftlob_gru_scan_fwd(T, B, H, *ptrs, _lib.stream_ptr(device=out[0].device)))
+    return out
 
 
 def scan_backward(d_hseq, hseq, gates, h0, done, w_hh):
     """hftlob_gru_scan_bwd on device tensors: (d_gi, d_gh_n, d_h0)."""
-    T, B, H = hseq.shape
-    d_hseq, hseq, gates, h0, w_hh = _f32(d_hseq), _f32(hseq), _f32(gates), _f32(h0), _f32(w_hh)
-    done = _u8(done)
-    ptrs = [_lib.ptr(x) for x in (d_hseq, hseq, gates, h0, done, w_hh)]
-    if d_hseq.shape != (T, B, H) or gates.shape != (T, B, 4 * H) or h0.shape != (B, H) or done.shape != (T, B) \
-            or w_hh.shape != (3 * H, H):
-        raise ValueError("gru_scan backward: shapes do not agree")
-    d_gi = torch.empty((T, B, 3 * H), dtype=torch.float32, device=hseq.device)
-    d_gh_n = torch.empty((T, B, H), dtype=torch.float32, device=hseq.device)
-    d_h0 = torch.empty((B, H), dtype=torch.float32, device=hseq.device)
-    _lib.check(_lib.lib().hftlob_gru_scan_bwd(T, B, H, *ptrs, _lib.ptr(d_gi), _lib.ptr(d_gh_n), _lib.ptr(d_h0),
-                                              _lib.stream_ptr(device=hseq.device)))
-    return d_gi, d_gh_n, d_h0
+    keep, ptrs, out = _bwd_group("gru_scan backward", (d_hseq, hseq, gates, h0, done, w_hh))
+    T, B, H = out[1].shape
+    _lib.check(_lib.lib().hftlob_gru_scan_bwd(T, B, H, *ptrs, _lib.stream_ptr(device=out[1].device)))
+    return out
 
 
 class GRUScan(torch.autograd.Function):
@@ -201,18 +214,11 @@ def scan_forward_grouped(groups, save_gates=True):
             raise ValueError("gru_scan grouped: a group is (gi [T, B, 3H], h0, done, w_hh, b_hh)")
     T, H = _check_groups("gru_scan grouped", [(g[0].shape[0], g[0].shape[1], g[0].shape[2] // 3) for g in groups])
     rows, keep, out = [], [], []
-    for k, (gi, h0, done, w_hh, b_hh) in enumerate(groups):
-        B = gi.shape[1]
-        gi, h0, w_hh, b_hh, done = _f32(gi), _f32(h0), _f32(w_hh), _f32(b_hh), _u8(done)
-        if h0.shape != (B, H) or done.shape != (T, B) or w_hh.shape != (3 * H, H) or b_hh.shape != (3 * H,):
-            raise ValueError(f"gru_scan grouped, group {k}: shapes gi {tuple(gi.shape)}, h0 {tuple(h0.shape)}, done "
-                             f"{tuple(done.shape)}, w_hh {tuple(w_hh.shape)}, b_hh {tuple(b_hh.shape)} do not agree")
-        ptrs = [_lib.ptr(x) for x in (gi, h0, done, w_hh, b_hh)]   # (a CPU tensor raises here)
-        hseq = torch.empty((T, B, H), dtype=torch.float32, device=gi.device)
-        gates = torch.empty((T, B, 4 * H), dtype=torch.float32, device=gi.device) if save[k] else None
-        rows.append(_lib.GruFwdGroup(B, *ptrs, _lib.ptr(hseq), _lib.ptr(gates)))
-        keep.append((gi, h0, done, w_hh, b_hh))   # (the converted copies live until the launch is made)
-        out.append((hseq, gates))
+    for k, g in enumerate(groups):
+        kept, ptrs, res = _fwd_group(f"gru_scan grouped, group {k}", g, save[k])
+        rows.append(_lib.GruFwdGroup(res[0].shape[1], *ptrs))
+        keep.append(kept)
+        out.append(res)
     arr = (_lib.GruFwdGroup * len(rows))(*rows)
     _lib.check(_lib.lib().hftlob_gru_scan_fwd_grouped(T, H, len(rows), arr, _lib.stream_ptr(device=out[0][0].device)))
     return out
@@ -227,19 +233,11 @@ def scan_backward_grouped(groups):
             raise ValueError("gru_scan grouped backward: a group is (d_hseq, hseq [T, B, H], gates, h0, done, w_hh)")
     T, H = _check_groups("gru_scan grouped backward", [tuple(g[1].shape) for g in groups])
     rows, keep, out = [], [], []
-    for k, (d_hseq, hseq, gates, h0, done, w_hh) in enumerate(groups):
-        B = hseq.shape[1]
-        d_hseq, hseq, gates, h0, w_hh, done = _f32(d_hseq), _f32(hseq), _f32(gates), _f32(h0), _f32(w_hh), _u8(done)
-        if d_hseq.shape != (T, B, H) or gates.shape != (T, B, 4 * H) or h0.shape != (B, H) or done.shape != (T, B) \
-                or w_hh.shape != (3 * H, H):
-            raise ValueError(f"gru_scan grouped backward, group {k}: shapes do not agree")
-        ptrs = [_lib.ptr(x) for x in (d_hseq, hseq, gates, h0, done, w_hh)]
-        d_gi = torch.empty((T, B, 3 * H), dtype=torch.float32, device=hseq.device)
-        d_gh_n = torch.empty((T, B, H), dtype=torch.float32, device=hseq.device)
-        d_h0 = torch.empty((B, H), dtype=torch.float32, device=hseq.device)
-        rows.append(_lib.GruBwdGroup(B, *ptrs, _lib.ptr(d_gi), _lib.ptr(d_gh_n), _lib.ptr(d_h0)))
-        keep.append((d_hseq, hseq, gates, h0, done, w_hh))
-        out.append((d_gi, d_gh_n, d_h0))
+    for k, g in enumerate(groups):
+        kept, ptrs, res = _bwd_group(f"gru_scan grouped backward, group {k}", g)
+        rows.append(_lib.GruBwdGroup(res[1].shape[1], *ptrs))
+        keep.append(kept)
+        out.append(res)
     arr = (_lib.GruBwdGroup * len(rows))(*rows)
     _lib.check(_lib.lib().hftlob_gru_scan_bwd_grouped(T, H, len(rows), arr, _lib.stream_ptr(device=out[0][0].device)))
     return out

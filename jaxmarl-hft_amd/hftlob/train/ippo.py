@@ -24,7 +24,8 @@ One network (and optimizer) per agent type, as the reference:
   and minibatch (``torch.distributed``, RCCL on ROCm).
 
 On the GPU each minibatch step (forward over the sequence, loss, backward,
-clipping, Adam) is captured once per agent type in a HIP graph and replayed
+clipping, Adam) is captured once per step group (an agent type, or with
+``GROUPED_SCAN`` all of them) in a HIP graph and replayed
 (``CUDA_GRAPHS``, single-process runs): a 64-step GRU unroll is thousands of small
 kernels, and replaying them as one graph removes their launch cost.
 
@@ -55,7 +56,7 @@ from __future__ import annotations
 import math
 import time
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Union
+from typing import Callable, Dict, List, Optional, Sequence, Union
 
 import torch
 import torch.nn as nn
@@ -75,14 +76,87 @@ def _per_type(v, n: int) -> list:
     return (v + [v[-1]] * n)[:n]
 
 
+@dataclass(frozen=True)
+class Switch:
+    """One on/off key of the config (default off).  The trainer carries its value as the attribute
+    ``key.lower()``, and ``main`` takes it as the command-line flag ``flag``."""
+    key: str
+    help: str           # the flag's help text
+    gpu: bool = True    # the trainer refuses the switch on any other device (there is no other path behind it)
+    # what a net the switch cannot take is told, without the "(agent type i)" that the trainer appends; else None
+    check: Optional[Callable[["ActorCriticRNN", Dict], Optional[str]]] = None
+
+    @property
+    def flag(self) -> str:
+        return "--" + self.key.lower().replace("_", "-")
+
+
+def _policy_step_check(lead: str):
+    """The per-net check of a switch that runs the fused policy step (``train.policy``); ``lead`` opens its text."""
+    def check(n, c):
+        D = n.embed.in_features
+        if policy_step_multi_supported(D, c["FC_DIM_SIZE"], c["GRU_HIDDEN_DIM"], n.heads):
+            return None
+        return (f"{lead} GRU_HIDDEN_DIM and FC_DIM_SIZE in {list(SUPPORTED_HIDDEN)}, an observation size <= "
+                f"{MAX_OBS_DIM} and <= {MAX_ACTIONS} actions (in each of <= {MAX_HEADS} heads), got "
+                f"{c['GRU_HIDDEN_DIM']}, {c['FC_DIM_SIZE']}, {D} and {n.heads}")
+    return check
+
+
+def _loss_check(n, c):
+    if not ppo_loss_supported(n.heads):
+        return f"FUSED_LOSS needs <= {MAX_ACTIONS} actions (in each of <= {MAX_HEADS} heads), got {n.heads}"
+
+
+def _opt_check(n, c):
+    if not adam_clip_supported(len(list(n.parameters()))):
+        return f"FUSED_OPT needs <= {MAX_TENSORS} parameter tensors in a net, got {len(list(n.parameters()))}"
+
+
+def _wgrad_check(n, c):
+    if not all(narrow_linear_supported(m.in_features, m.out_features) for m in (n.embed, n.actor2, n.critic2)):
+        return (f"FUSED_WGRAD needs GRU_HIDDEN_DIM and FC_DIM_SIZE in {list(SUPPORTED_Q)}, an observation size <= "
+                f"{MAX_P} and <= {MAX_P} actions over all heads, got {c['GRU_HIDDEN_DIM']}, {c['FC_DIM_SIZE']}, "
+                f"{n.embed.in_features} and {sum(n.heads)}")
+
+
+def _wgrad_wide_check(n, c):
+    sizes = ((n.gru.input_size, 3 * n.hidden), (n.hidden, 3 * n.hidden), (n.actor1.in_features, n.actor1.out_features),
+             (n.critic1.in_features, n.critic1.out_features))
+    if not all(wide_linear_supported(i, o) for i, o in sizes):
+        return (f"FUSED_WGRAD_WIDE needs GRU_HIDDEN_DIM and FC_DIM_SIZE in {list(SUPPORTED_Q)}, got "
+                f"{c['GRU_HIDDEN_DIM']} and {c['FC_DIM_SIZE']}")
+
+
+# Every switch, in the order the trainer checks them.  The module docstring says what each one does; what a
+# switch needs beyond a device and a per-net check (FUSED_GRU's hidden size and its CPU rule, GROUPED_SCAN's
+# three conditions, CALC_EVAL's eval env) is in IPPOTrainer.__init__.
+SWITCHES = [
+    Switch("FUSED_GRU", "the PPO update's GRU scan as the fused HIP operators", gpu=False),   # on the CPU: the loop
+    Switch("FUSED_POLICY", "the rollout's policy step, sample and log-prob as one fused HIP launch",
+           check=_policy_step_check("FUSED_POLICY needs")),
+    Switch("FUSED_LOSS", "the update's GAE and PPO loss (with its gradient) as fused HIP launches", check=_loss_check),
+    Switch("FUSED_OPT", "the minibatch step's global-norm clip and Adam step as two fused HIP launches",
+           check=_opt_check),
+    Switch("GROUPED_SCAN", "the agent types' minibatch steps in lockstep, their GRU scans one HIP launch per direction "
+           "(needs --fused-gru)", gpu=False),   # FUSED_GRU's device rule: on the CPU the scans are the loops
+    Switch("FUSED_WGRAD", "the narrow layers' (embed, actor2, critic2) weight and bias gradients as two fused HIP "
+           "launches each", check=_wgrad_check),
+    Switch("FUSED_WGRAD_WIDE", "the wide layers' (the GRU's two weight matrices, actor1, critic1) weight and bias "
+           "gradients as two fused HIP launches each", check=_wgrad_wide_check),
+    Switch("CALC_EVAL", "CALC_EVAL: after every update NUM_STEPS_EVAL sampled steps in a separate eval env (the same "
+           "config, a synthetic day of another seed), logged as avg_reward_eval",
+           check=_policy_step_check("CALC_EVAL runs the fused policy step: it needs")),
+]
+
+
 def default_config(**kw) -> Dict:
-    """The reference's ippo_rnn_JAXMARL_2player.yaml hyper-parameters (training keys only)."""
+    """The reference's ippo_rnn_JAXMARL_2player.yaml hyper-parameters (training keys only), every switch off."""
     c = {"LR": [2.5e-4, 2.5e-4], "NUM_ENVS": 4096, "NUM_STEPS": 64, "GRU_HIDDEN_DIM": 256, "FC_DIM_SIZE": 256,
          "TOTAL_TIMESTEPS": 5e8, "UPDATE_EPOCHS": 4, "NUM_MINIBATCHES": 4, "GAMMA": [0.999999999, 0.999],
          "GAE_LAMBDA": [0.85, 0.9], "CLIP_EPS": 0.2, "ENT_COEF": [0.01, 0.01], "VF_COEF": [0.5, 0.5],
          "MAX_GRAD_NORM": [0.5, 0.5], "ANNEAL_LR": [True, True], "NUM_AGENTS_PER_TYPE": [1, 1], "SEED": 2,
-         "CUDA_GRAPHS": True, "FUSED_GRU": False, "FUSED_POLICY": False, "FUSED_LOSS": False,
-         "FUSED_OPT": False, "GROUPED_SCAN": False, "FUSED_WGRAD": False, "FUSED_WGRAD_WIDE": False, "CALC_EVAL": False,
+         "CUDA_GRAPHS": True, **{sw.key: False for sw in SWITCHES},
          "NUM_STEPS_EVAL": None}   # NUM_STEPS_EVAL None: NUM_STEPS
     c.update(kw)
     return c
@@ -127,15 +201,12 @@ class ActorCriticRNN(nn.Module):
         # gradients through train.wgrad.wide_linear and train.gru.weight_grads_fused; the trainer sets it
         self.fused_wgrad_wide = False
 
-    def _wide(self, x: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-        """A wide layer of the sequence forward: ``F.linear``, with ``fused_wgrad_wide`` the fused weight
-        gradient behind it."""
-        return wide_linear(x, w, b) if self.fused_wgrad_wide else F.linear(x, w, b)
-
-    def _linear(self, m: nn.Linear, x: torch.Tensor) -> torch.Tensor:
-        """A narrow layer of the sequence forward: the module itself, or with ``fused_wgrad`` the same
-        ``F.linear`` of its own weight and bias with the fused weight gradient behind it."""
-        return narrow_linear(x, m.weight, m.bias) if self.fused_wgrad else m(x)
+    def _linear(self, x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, wide: bool = False) -> torch.Tensor:
+        """A layer of the sequence forward: ``F.linear`` (what a Linear module is on its own weight and bias),
+        with the fused weight gradient behind it where the layer's flag is set: ``fused_wgrad`` for a narrow
+        layer, ``fused_wgrad_wide`` for a wide one."""
+        on, fused = (self.fused_wgrad_wide, wide_linear) if wide else (self.fused_wgrad, narrow_linear)
+        return fused(x, w, b) if on else F.linear(x, w, b)
 
     def action_shape(self, *lead: int) -> tuple:
         """The shape of the public action tensor of ``lead`` actors: one word each for a Discrete space,
@@ -170,39 +241,39 @@ class ActorCriticRNN(nn.Module):
     def gi_all(self, obs: torch.Tensor) -> torch.Tensor:
         """The input side of ``forward``: the embedding and the GRU's input projection over all T at once,
         [T, B, 3H] in gate order (r, z, n)."""
-        return self._wide(F.relu(self._linear(self.embed, obs)), self.gru.weight_ih, self.gru.bias_ih)
+        e = self._linear(obs, self.embed.weight, self.embed.bias)
+        return self._linear(F.relu(e), self.gru.weight_ih, self.gru.bias_ih, wide=True)
 
     def head_outputs(self, hseq: torch.Tensor):
         """The heads of ``forward`` on the scan's hseq [T, B, H]: logits [T, B, A], values [T, B]."""
-        a1 = self._wide(hseq, self.actor1.weight, self.actor1.bias)
-        c1 = self._wide(hseq, self.critic1.weight, self.critic1.bias)
-        return self._linear(self.actor2, F.relu(a1)), self._linear(self.critic2, F.relu(c1)).squeeze(-1)
+        a1 = self._linear(hseq, self.actor1.weight, self.actor1.bias, wide=True)
+        c1 = self._linear(hseq, self.critic1.weight, self.critic1.bias, wide=True)
+        return (self._linear(F.relu(a1), self.actor2.weight, self.actor2.bias),
+                self._linear(F.relu(c1), self.critic2.weight, self.critic2.bias).squeeze(-1))
 
     def forward(self, h0: torch.Tensor, obs: torch.Tensor, dones: torch.Tensor):
         """A sequence [T, B, ...] from carry h0 (the ScannedRNN scan): logits [T, B, A], values [T, B].
         The same cell as ``step``; the input-side GEMMs (embedding, the GRU's input
         projection, both heads) run once over all T, only h @ W_hh stays in the scan: the loop
         of ``scan_loop``, or with ``fused`` set one HIP launch forward and one backward."""
-        if self.fused:
-            hseq = gru_scan(self.gi_all(obs), h0, dones, self.gru.weight_hh, self.gru.bias_hh, self.fused_wgrad_wide)
-        else:
-            hseq = self.scan_loop(self.gi_all(obs), h0, dones, self.gru.weight_hh, self.gru.bias_hh)
-        return self.head_outputs(hseq)
+        return self.forward_grouped([self], [h0], [obs], [dones])[0]
 
     @staticmethod
     def forward_grouped(nets, h0s, obss, dones):
         """``forward`` of several independent nets on their own sequences: a list of (logits, values), net
-        k's equal bit for bit to ``nets[k](h0s[k], obss[k], dones[k])``.  With every net ``fused`` the
-        scans are one HIP launch forward and one backward for all the nets (``gru_scan_grouped``; the
-        nets share T and the hidden size, each has its own B); otherwise each net runs its ``scan_loop``."""
+        k's what the net gives alone, bit for bit.  Unless every net is ``fused`` each net's scan is its
+        ``scan_loop``.  With every net ``fused``, one net's scan is ``gru_scan`` and several nets' scans are
+        one HIP launch forward and one backward for all of them (``gru_scan_grouped``; the nets share T and
+        the hidden size, each has its own B)."""
         gis = [net.gi_all(obs) for net, obs in zip(nets, obss)]
-        if all(net.fused for net in nets):
-            hseqs = gru_scan_grouped(gis, h0s, dones, [net.gru.weight_hh for net in nets],
-                                     [net.gru.bias_hh for net in nets],
-                                     fused_wgrad=all(net.fused_wgrad_wide for net in nets))
+        w_hhs, b_hhs = [net.gru.weight_hh for net in nets], [net.gru.bias_hh for net in nets]
+        fused_wgrad = all(net.fused_wgrad_wide for net in nets)
+        if not all(net.fused for net in nets):
+            hseqs = [net.scan_loop(*xs) for net, *xs in zip(nets, gis, h0s, dones, w_hhs, b_hhs)]
+        elif len(nets) == 1:
+            hseqs = [gru_scan(gis[0], h0s[0], dones[0], w_hhs[0], b_hhs[0], fused_wgrad)]
         else:
-            hseqs = [net.scan_loop(gi, h0, d, net.gru.weight_hh, net.gru.bias_hh)
-                     for net, gi, h0, d in zip(nets, gis, h0s, dones)]
+            hseqs = gru_scan_grouped(gis, h0s, dones, w_hhs, b_hhs, fused_wgrad=fused_wgrad)
         return [net.head_outputs(hseq) for net, hseq in zip(nets, hseqs)]
 
 
@@ -308,9 +379,8 @@ class IPPOTrainer:
         if n_global % world:
             raise ValueError(f"NUM_ENVS ({n_global}) must be a multiple of the world size ({world})")
         # GROUPED_SCAN: the agent types' minibatch steps in lockstep, their scans one launch per direction
-        # (train.gru.gru_scan_grouped).  It follows FUSED_GRU's device rule: on the CPU the scans are the loops
-        self.grouped_scan = bool(c.get("GROUPED_SCAN", False))
-        if self.grouped_scan:
+        # (train.gru.gru_scan_grouped)
+        if c.get("GROUPED_SCAN", False):
             if not c.get("FUSED_GRU", False):
                 raise ValueError("GROUPED_SCAN needs FUSED_GRU")
             if nt > MAX_GROUPS:
@@ -338,87 +408,32 @@ class IPPOTrainer:
                                  f"got {c['GRU_HIDDEN_DIM']}")
             for n in self.nets:
                 n.fused = self.device.type == "cuda"
-        # FUSED_POLICY: the rollout's policy step, sample and log-prob as one HIP launch per agent type
-        # and step (train.policy.policy_step; GPU only, and there is no other path behind the switch)
-        self.fused_policy = bool(c.get("FUSED_POLICY", False))
-        if self.fused_policy:
-            if self.device.type != "cuda":
-                raise ValueError(f"FUSED_POLICY needs a GPU device, got {self.device}")
-            for i, n in enumerate(self.nets):
-                D = n.embed.in_features
-                if not policy_step_multi_supported(D, c["FC_DIM_SIZE"], c["GRU_HIDDEN_DIM"], n.heads):
-                    raise ValueError(f"FUSED_POLICY needs GRU_HIDDEN_DIM and FC_DIM_SIZE in {list(SUPPORTED_HIDDEN)}, "
-                                     f"an observation size <= {MAX_OBS_DIM} and <= {MAX_ACTIONS} actions (in each of "
-                                     f"<= {MAX_HEADS} heads), got {c['GRU_HIDDEN_DIM']}, {c['FC_DIM_SIZE']}, {D} and "
-                                     f"{n.heads} (agent type {i})")
-        # FUSED_LOSS: the update's GAE as one HIP launch and the minibatch step's loss with its gradient as
-        # three (train.loss.gae, train.loss.ppo_loss_fused; GPU only, and there is no other path behind the switch)
-        self.fused_loss = bool(c.get("FUSED_LOSS", False))
-        if self.fused_loss:
-            if self.device.type != "cuda":
-                raise ValueError(f"FUSED_LOSS needs a GPU device, got {self.device}")
-            for i, n in enumerate(self.nets):
-                if not ppo_loss_supported(n.heads):
-                    raise ValueError(f"FUSED_LOSS needs <= {MAX_ACTIONS} actions (in each of <= {MAX_HEADS} heads), "
-                                     f"got {n.heads} (agent type {i})")
-        # FUSED_OPT: the minibatch step's global-norm clip and Adam step as two HIP launches
-        # (train.optim.adam_clip_step; GPU only, and there is no other path behind the switch)
-        self.fused_opt = bool(c.get("FUSED_OPT", False))
-        if self.fused_opt:
-            if self.device.type != "cuda":
-                raise ValueError(f"FUSED_OPT needs a GPU device, got {self.device}")
-            for i, n in enumerate(self.nets):
-                if not adam_clip_supported(len(list(n.parameters()))):
-                    raise ValueError(f"FUSED_OPT needs <= {MAX_TENSORS} parameter tensors in a net, got "
-                                     f"{len(list(n.parameters()))} (agent type {i})")
-        # FUSED_WGRAD: the weight and bias gradients of embed, actor2 and critic2 in the minibatch step as two HIP
-        # launches each (train.wgrad.narrow_linear; GPU only, and there is no other path behind the switch)
-        self.fused_wgrad = bool(c.get("FUSED_WGRAD", False))
-        if self.fused_wgrad:
-            if self.device.type != "cuda":
-                raise ValueError(f"FUSED_WGRAD needs a GPU device, got {self.device}")
-            for i, n in enumerate(self.nets):
-                for m in (n.embed, n.actor2, n.critic2):
-                    if not narrow_linear_supported(m.in_features, m.out_features):
-                        raise ValueError(f"FUSED_WGRAD needs GRU_HIDDEN_DIM and FC_DIM_SIZE in {list(SUPPORTED_Q)}, an "
-                                         f"observation size <= {MAX_P} and <= {MAX_P} actions over all heads, got "
-                                         f"{c['GRU_HIDDEN_DIM']}, {c['FC_DIM_SIZE']}, {n.embed.in_features} and "
-                                         f"{sum(n.heads)} (agent type {i})")
-                n.fused_wgrad = True
-        # FUSED_WGRAD_WIDE: the weight and bias gradients of gru.weight_ih, actor1 and critic1, and with the fused
-        # scan of gru.weight_hh, as two HIP launches each (train.wgrad.wide_linear, train.gru.weight_grads_fused;
-        # GPU only, and there is no other path behind the switch)
-        self.fused_wgrad_wide = bool(c.get("FUSED_WGRAD_WIDE", False))
-        if self.fused_wgrad_wide:
-            if self.device.type != "cuda":
-                raise ValueError(f"FUSED_WGRAD_WIDE needs a GPU device, got {self.device}")
-            for i, n in enumerate(self.nets):
-                for in_f, out_f in ((n.gru.input_size, 3 * n.hidden), (n.hidden, 3 * n.hidden),
-                                    (n.actor1.in_features, n.actor1.out_features),
-                                    (n.critic1.in_features, n.critic1.out_features)):
-                    if not wide_linear_supported(in_f, out_f):
-                        raise ValueError(f"FUSED_WGRAD_WIDE needs GRU_HIDDEN_DIM and FC_DIM_SIZE in {list(SUPPORTED_Q)}, "
-                                         f"got {c['GRU_HIDDEN_DIM']} and {c['FC_DIM_SIZE']} (agent type {i})")
-                n.fused_wgrad_wide = True
         # CALC_EVAL (:461-482, 876-975): after every update NUM_STEPS_EVAL sampled steps of the current nets
         # in a separate eval env, through the fused policy step and the tally launch (evaluate_policy)
-        self.calc_eval = bool(c.get("CALC_EVAL", False))
         self.updates_done = 0
-        if self.calc_eval:
+        if c.get("CALC_EVAL", False):
             self.T_eval = int(c.get("NUM_STEPS_EVAL") or self.T)
             if self.T_eval < 1:
                 raise ValueError(f"NUM_STEPS_EVAL must be >= 1, got {self.T_eval}")
             if eval_env is None or not getattr(eval_env, "return_info", False):
                 raise ValueError("CALC_EVAL needs eval_env, a second MARLEnv built with return_info=True")
-            if self.device.type != "cuda":
-                raise ValueError(f"CALC_EVAL needs a GPU device, got {self.device}")
+        # every switch as the attribute of its name in lower case (fused_policy, fused_loss, fused_opt, grouped_scan,
+        # fused_wgrad, fused_wgrad_wide, calc_eval, ...); one that is on passes its device and per-net checks
+        for sw in SWITCHES:
+            on = bool(c.get(sw.key, False))
+            setattr(self, sw.key.lower(), on)
+            if not on:
+                continue
+            if sw.gpu and self.device.type != "cuda":
+                raise ValueError(f"{sw.key} needs a GPU device, got {self.device}")
             for i, n in enumerate(self.nets):
-                if not policy_step_multi_supported(n.embed.in_features, c["FC_DIM_SIZE"], c["GRU_HIDDEN_DIM"], n.heads):
-                    raise ValueError(f"CALC_EVAL runs the fused policy step: it needs GRU_HIDDEN_DIM and FC_DIM_SIZE in "
-                                     f"{list(SUPPORTED_HIDDEN)}, an observation size <= {MAX_OBS_DIM} and <= "
-                                     f"{MAX_ACTIONS} actions (in each of <= {MAX_HEADS} heads), got "
-                                     f"{c['GRU_HIDDEN_DIM']}, {c['FC_DIM_SIZE']}, {n.embed.in_features} and {n.heads} "
-                                     f"(agent type {i})")
+                err = sw.check(n, c) if sw.check else None
+                if err:
+                    raise ValueError(f"{err} (agent type {i})")
+        for n in self.nets:   # the layers' weight gradients in the minibatch step (train.wgrad)
+            n.fused_wgrad, n.fused_wgrad_wide = self.fused_wgrad, self.fused_wgrad_wide
+        # the sets of agent types whose minibatch steps run as one: every type on its own, or all of them in lockstep
+        groups = [list(range(nt))] if self.grouped_scan else [[i] for i in range(nt)]
         # HIP-graph minibatch steps: single process on the GPU (the grad all-reduce stays eager)
         self.graphs = bool(c.get("CUDA_GRAPHS", False)) and self.device.type == "cuda" and world == 1
         if self.graphs or self.fused_opt:  # capturable Adam: step counter and lr live on the device
@@ -430,7 +445,8 @@ class IPPOTrainer:
             for opt in self.opts:
                 init_adam_state(opt)
         self._roll = None        # the captured rollout graph (False: not capturable, stays eager)
-        self._joint = {"warm": 0, "graph": None, "out": None}   # GROUPED_SCAN: the joint step's graph, as _st[i]'s
+        # one record per step group: its types, the eager steps run before the capture, the graph and its outputs
+        self._steps = [{"types": g, "warm": 0, "graph": None, "out": None} for g in groups]
         self.opt_count = [0] * nt
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(c["SEED"] + 1000 * rank)
@@ -465,6 +481,12 @@ class IPPOTrainer:
                             reward=torch.empty((T, n), device=self.device),
                             log_prob=torch.empty((T, n), device=self.device))
                     for i, n in enumerate(self.n_actors)]
+        # the fixed-address inputs of each agent type's minibatch steps (what a captured graph reads)
+        self._st = [{"h0": torch.empty((n, c["GRU_HIDDEN_DIM"]), device=self.device),
+                     "adv": torch.empty((T, n), device=self.device),
+                     "tgt": torch.empty((T, n), device=self.device),
+                     "idx": torch.zeros(n // c["NUM_MINIBATCHES"], dtype=torch.long, device=self.device)}
+                    for n in self.n_actors]
 
     def _next_keys(self) -> torch.Tensor:
         """rng, _rng = split(rng); rng_step = split(_rng, NUM_ENVS) (:613-614)."""
@@ -479,7 +501,7 @@ class IPPOTrainer:
         if not self.graphs or self._roll is False:
             return self._rollout()
         if self._roll is None:  # one eager rollout (warm-up), then capture; capture runs nothing
-            self._rollout_side()
+            self._on_side_stream(self._rollout)
             self._roll = 0
             return None
         if self._roll == 0:
@@ -495,12 +517,14 @@ class IPPOTrainer:
         self._roll.replay()
         return None
 
-    def _rollout_side(self) -> None:
+    def _on_side_stream(self, fn):
+        """fn() on a side stream between two joins with the current one: how eager work runs ahead of a capture."""
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
-            self._rollout()
+            r = fn()
         torch.cuda.current_stream(self.device).wait_stream(side)
+        return r
 
     def _rollout(self) -> None:
         for t in range(self.T):
@@ -536,125 +560,63 @@ class IPPOTrainer:
                 self.last_obs[i].copy_(obs[i].reshape(self.n_actors[i], -1))
                 self.last_done[i].copy_(dones["agents"][i].reshape(-1))
 
-    def _static(self, i: int, n: int, mb: int):
-        """Fixed-address inputs of agent type i's minibatch step (what a captured graph reads)."""
-        if not hasattr(self, "_st"):
-            self._st = [None] * self.n_types
-        if self._st[i] is None:
-            T, H = self.T, self.c["GRU_HIDDEN_DIM"]
-            self._st[i] = {"h0": torch.empty((n, H), device=self.device),
-                           "adv": torch.empty((T, n), device=self.device),
-                           "tgt": torch.empty((T, n), device=self.device),
-                           "idx": torch.zeros(n // mb, dtype=torch.long, device=self.device),
-                           "warm": 0, "graph": None, "out": None}
-        return self._st[i]
-
-    def _mb_step(self, i: int) -> torch.Tensor:
-        """One PPO minibatch step of agent type i from the static inputs: forward over the
-        sequences, loss, backward, grad pmean (multi-rank), global-norm clip, Adam."""
-        c, net, opt, b, st = self.c, self.nets[i], self.opts[i], self.buf[i], self._st[i]
-        idx = st["idx"]
-        logits, values = net(st["h0"][idx], b.obs[:, idx], b.done[:, idx])
-        loss_fn = ppo_loss_fused if self.fused_loss else ppo_loss_multi
-        out = loss_fn(logits, values, b.action[:, idx].view(self.T, -1, len(net.heads)), b.value[:, idx],
-                      b.log_prob[:, idx], st["adv"][:, idx], st["tgt"][:, idx], c["CLIP_EPS"], c["VF_COEF"][i],
-                      c["ENT_COEF"][i], net.heads)
-        out[0].backward()
-        if self.dist is not None and self.dist.get_world_size() > 1:
-            _average_grads(list(net.parameters()), self.dist)
-        if self.fused_opt:
-            adam_clip_step(opt, c["MAX_GRAD_NORM"][i])
-        else:
-            torch.nn.utils.clip_grad_norm_(net.parameters(), c["MAX_GRAD_NORM"][i])
-            opt.step()
-        return torch.stack([x.detach() for x in out])
-
-    def _minibatch(self, i: int) -> torch.Tensor:
-        st, opt = self._st[i], self.opts[i]
-        if not self.graphs:
-            opt.zero_grad(set_to_none=True)
-            return self._mb_step(i)
-        if st["graph"] is None and st["warm"] < 2:  # eager steps on a side stream before capture
-            side = torch.cuda.Stream(self.device)
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):
-                opt.zero_grad(set_to_none=True)
-                r = self._mb_step(i)
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            st["warm"] += 1
-            return r
-        if st["graph"] is None:  # capture once (nothing runs), then replay below
-            opt.zero_grad(set_to_none=True)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                st["out"] = self._mb_step(i)
-            st["graph"] = g
-        st["graph"].replay()
-        return st["out"].clone()
-
-    def _joint_step(self) -> List[torch.Tensor]:
-        """GROUPED_SCAN: one PPO minibatch step of every agent type from the static inputs, the types'
-        scans grouped (``forward_grouped``); per type what ``_mb_step`` does (single process: no pmean)."""
+    def _step(self, types: List[int]) -> List[torch.Tensor]:
+        """One PPO minibatch step of the agent types ``types`` from their static inputs: the forward over the
+        sequences (``forward_grouped``: several types' scans are grouped), each type's loss, one backward, then
+        per type the grad pmean (multi-rank), the global-norm clip and Adam; returns each type's loss scalars."""
         c, T = self.c, self.T
-        idxs = [st["idx"] for st in self._st]
-        fw = ActorCriticRNN.forward_grouped(self.nets, [st["h0"][idx] for st, idx in zip(self._st, idxs)],
-                                            [b.obs[:, idx] for b, idx in zip(self.buf, idxs)],
-                                            [b.done[:, idx] for b, idx in zip(self.buf, idxs)])
+        nets, bufs, sts = ([x[i] for i in types] for x in (self.nets, self.buf, self._st))
+        idxs = [st["idx"] for st in sts]
+        fw = ActorCriticRNN.forward_grouped(nets, [st["h0"][idx] for st, idx in zip(sts, idxs)],
+                                            [b.obs[:, idx] for b, idx in zip(bufs, idxs)],
+                                            [b.done[:, idx] for b, idx in zip(bufs, idxs)])
         loss_fn = ppo_loss_fused if self.fused_loss else ppo_loss_multi
         outs = []
-        for i, (net, b, st, idx, (logits, values)) in enumerate(zip(self.nets, self.buf, self._st, idxs, fw)):
+        for i, net, b, st, idx, (logits, values) in zip(types, nets, bufs, sts, idxs, fw):
             outs.append(loss_fn(logits, values, b.action[:, idx].view(T, -1, len(net.heads)), b.value[:, idx],
                                 b.log_prob[:, idx], st["adv"][:, idx], st["tgt"][:, idx], c["CLIP_EPS"], c["VF_COEF"][i],
                                 c["ENT_COEF"][i], net.heads))
         # the list of totals, not their sum: the grouped scan's backward runs once, when every type's
         # gradient of its hseq has arrived, and no type's gradient passes through an addition
         torch.autograd.backward([out[0] for out in outs])
-        for i, (net, opt) in enumerate(zip(self.nets, self.opts)):
+        for i, net in zip(types, nets):
+            if self.dist is not None and self.dist.get_world_size() > 1:
+                _average_grads(list(net.parameters()), self.dist)
             if self.fused_opt:
-                adam_clip_step(opt, c["MAX_GRAD_NORM"][i])
+                adam_clip_step(self.opts[i], c["MAX_GRAD_NORM"][i])
             else:
                 torch.nn.utils.clip_grad_norm_(net.parameters(), c["MAX_GRAD_NORM"][i])
-                opt.step()
+                self.opts[i].step()
         return [torch.stack([x.detach() for x in out]) for out in outs]
 
-    def _zero_grads(self) -> None:
-        for opt in self.opts:
-            opt.zero_grad(set_to_none=True)
-
-    def _joint_minibatch(self) -> List[torch.Tensor]:
-        """``_minibatch`` for the joint step: eager, or two warm-ups on a side stream, one capture, replays."""
-        j = self._joint
-        if not self.graphs:
-            self._zero_grads()
-            return self._joint_step()
-        if j["graph"] is None and j["warm"] < 2:
-            side = torch.cuda.Stream(self.device)
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):
-                self._zero_grads()
-                r = self._joint_step()
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            j["warm"] += 1
-            return r
-        if j["graph"] is None:
-            self._zero_grads()
+    def _run_step(self, s: Dict) -> List[torch.Tensor]:
+        """``_step`` of the step group with record ``s``: eager, or with CUDA_GRAPHS two eager steps on a side
+        stream, then one capture (which runs nothing), then replays."""
+        types = s["types"]
+        if s["graph"] is None:
+            for i in types:
+                self.opts[i].zero_grad(set_to_none=True)
+            if not self.graphs:
+                return self._step(types)
+            if s["warm"] < 2:
+                r = self._on_side_stream(lambda: self._step(types))
+                s["warm"] += 1
+                return r
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                j["out"] = self._joint_step()
-            j["graph"] = g
-        j["graph"].replay()
-        return [o.clone() for o in j["out"]]
+                s["out"] = self._step(types)
+            s["graph"] = g
+        s["graph"].replay()
+        return [o.clone() for o in s["out"]]
 
-    def _prepare(self, i: int, h0: torch.Tensor) -> Dict:
+    def _prepare(self, i: int, h0: torch.Tensor) -> None:
         """After the rollout: agent type i's last value, GAE and the static inputs of its minibatch steps."""
-        c, net, b = self.c, self.nets[i], self.buf[i]
-        st = self._static(i, self.n_actors[i], c["NUM_MINIBATCHES"])
+        c, net, b, st = self.c, self.nets[i], self.buf[i], self._st[i]
         with torch.no_grad():
             _, _, last_val = net.step(self.h[i], self.last_obs[i], self.last_done[i])
             gae_fn = gae_fused if self.fused_loss else calculate_gae
             adv, targets = gae_fn(b.reward, b.value, b.global_done, last_val, c["GAMMA"][i], c["GAE_LAMBDA"][i])
             st["h0"].copy_(h0); st["adv"].copy_(adv); st["tgt"].copy_(targets)
-        return st
 
     def _set_lr(self, i: int) -> None:
         """Agent type i's annealed learning rate for its next optimiser step, from its own ``opt_count``."""
@@ -668,51 +630,33 @@ class IPPOTrainer:
                 else:
                     g["lr"] = lr
 
-    def _update_joint(self, h0: List[torch.Tensor]) -> List[torch.Tensor]:
-        """GROUPED_SCAN: every type's minibatch steps in lockstep; returns the types' summed loss scalars.
-        The permutations are drawn up front in the order the per-type path draws them (type 0's epochs,
-        then type 1's, ...), so the generator goes through the same sequence."""
-        c, nt, mb = self.c, self.n_types, self.c["NUM_MINIBATCHES"]
-        for i in range(nt):
-            self._prepare(i, h0[i])
-        perms = [[torch.randperm(n, device=self.device, generator=self.gen).view(mb, n // mb)
-                  for _ in range(c["UPDATE_EPOCHS"])] for n in self.n_actors]
-        stats = [torch.zeros(6, device=self.device) for _ in range(nt)]
-        for e in range(c["UPDATE_EPOCHS"]):
-            for m in range(mb):
-                for i in range(nt):
-                    self._set_lr(i)
-                    self._st[i]["idx"].copy_(perms[i][e][m])
-                for i, r in enumerate(self._joint_minibatch()):
-                    stats[i] += r
-                    self.opt_count[i] += 1
-        return stats
-
     def update(self) -> Dict:
-        """One _update_step: rollout, GAE, UPDATE_EPOCHS x NUM_MINIBATCHES PPO steps per agent type."""
-        c = self.c
+        """One _update_step: rollout, GAE, UPDATE_EPOCHS x NUM_MINIBATCHES PPO steps per agent type, one
+        step group after the other (every type on its own, or with GROUPED_SCAN all the types in lockstep)."""
+        c, mb = self.c, self.c["NUM_MINIBATCHES"]
         h0 = [h.clone() for h in self.h]
         self.rollout()
-        metrics = {"loss": [], "avg_reward": []}
-        joint = self._update_joint(h0) if self.grouped_scan else None
-        for i, net in enumerate(self.nets):
-            b = self.buf[i]
-            n, mb = self.n_actors[i], c["NUM_MINIBATCHES"]
-            if joint is not None:
-                stats = joint[i]
-            else:
-                st = self._prepare(i, h0[i])
-                stats = torch.zeros(6, device=self.device)
-                for _ in range(c["UPDATE_EPOCHS"]):
-                    perm = torch.randperm(n, device=self.device, generator=self.gen)
-                    for idx in perm.view(mb, n // mb):
+        for i in range(self.n_types):
+            self._prepare(i, h0[i])
+        # every permutation up front, type 0's epochs, then type 1's, ...: the generator goes through one
+        # sequence whatever the step groups are
+        perms = [[torch.randperm(n, device=self.device, generator=self.gen).view(mb, n // mb)
+                  for _ in range(c["UPDATE_EPOCHS"])] for n in self.n_actors]
+        stats = [torch.zeros(6, device=self.device) for _ in range(self.n_types)]
+        for s in self._steps:
+            for e in range(c["UPDATE_EPOCHS"]):
+                for m in range(mb):
+                    for i in s["types"]:
                         self._set_lr(i)
-                        st["idx"].copy_(idx)
-                        stats += self._minibatch(i)
+                        self._st[i]["idx"].copy_(perms[i][e][m])
+                    for i, r in zip(s["types"], self._run_step(s)):
+                        stats[i] += r
                         self.opt_count[i] += 1
-            stats /= c["UPDATE_EPOCHS"] * mb
+        metrics = {"loss": [], "avg_reward": []}
+        for i, b in enumerate(self.buf):
+            stats[i] /= c["UPDATE_EPOCHS"] * mb
             metrics["loss"].append(dict(zip(("total_loss", "value_loss", "actor_loss", "entropy", "approx_kl",
-                                             "clip_frac"), stats)))
+                                             "clip_frac"), stats[i])))
             metrics["avg_reward"].append(b.reward.mean())
         if self.calc_eval:
             ev = self.evaluate(self.updates_done)
@@ -757,7 +701,7 @@ class IPPOTrainer:
     def load_checkpoint(self, path: str) -> None:
         """Restores what ``save_checkpoint`` wrote into this trainer (same env and sizes).  The
         parameters are copied in place (a captured rollout stays valid); the optimisers get new
-        state tensors, so the minibatch graphs (the joint one included) are captured again at the next update."""
+        state tensors, so the minibatch steps' graphs are captured again at the next update."""
         ck = _read_checkpoint(path)
         if len(ck["nets"]) != self.n_types:
             raise ValueError(f"{path}: {len(ck['nets'])} agent types, this trainer has {self.n_types}")
@@ -771,10 +715,8 @@ class IPPOTrainer:
             if self.fused_opt:   # (a checkpoint from before the first step carries no state)
                 init_adam_state(opt)
         self.opt_count = list(ck["opt_count"])
-        for st in getattr(self, "_st", []):
-            if st is not None:
-                st.update(warm=0, graph=None, out=None)
-        self._joint.update(warm=0, graph=None, out=None)
+        for s in self._steps:
+            s.update(warm=0, graph=None, out=None)
 
 
 CHECKPOINT_FORMAT = "hftlob-ippo-1"
@@ -831,8 +773,7 @@ def train(env: MARLEnv, config: Dict, n_updates: Optional[int] = None, dist=None
 
 def main(argv=None) -> None:
     """python -m hftlob.train.ippo [--rl-config ippo.yaml] [--env-config 2_player_fq_fqc] [--updates N]
-    [--fused-gru] [--fused-policy] [--fused-loss] [--fused-opt] [--grouped-scan] [--fused-wgrad]
-    [--fused-wgrad-wide]"""
+    [switch flags: one per row of SWITCHES, --fused-gru ... --calc-eval]"""
     import argparse
     import json
     import yaml
@@ -842,25 +783,8 @@ def main(argv=None) -> None:
     ap.add_argument("--env-config", default="2_player_fq_fqc", help="JSON path or builtin config name")
     ap.add_argument("--updates", type=int, default=2)
     ap.add_argument("--envs", type=int, default=None)
-    ap.add_argument("--fused-gru", action="store_true", help="the PPO update's GRU scan as the fused HIP operators")
-    ap.add_argument("--fused-policy", action="store_true",
-                    help="the rollout's policy step, sample and log-prob as one fused HIP launch")
-    ap.add_argument("--fused-loss", action="store_true",
-                    help="the update's GAE and PPO loss (with its gradient) as fused HIP launches")
-    ap.add_argument("--fused-opt", action="store_true",
-                    help="the minibatch step's global-norm clip and Adam step as two fused HIP launches")
-    ap.add_argument("--grouped-scan", action="store_true",
-                    help="the agent types' minibatch steps in lockstep, their GRU scans one HIP launch per direction "
-                         "(needs --fused-gru)")
-    ap.add_argument("--fused-wgrad", action="store_true",
-                    help="the narrow layers' (embed, actor2, critic2) weight and bias gradients as two fused HIP "
-                         "launches each")
-    ap.add_argument("--fused-wgrad-wide", action="store_true",
-                    help="the wide layers' (the GRU's two weight matrices, actor1, critic1) weight and bias gradients "
-                         "as two fused HIP launches each")
-    ap.add_argument("--calc-eval", action="store_true",
-                    help="CALC_EVAL: after every update NUM_STEPS_EVAL sampled steps in a separate eval env (the same "
-                         "config, a synthetic day of another seed), logged as avg_reward_eval")
+    for sw in SWITCHES:
+        ap.add_argument(sw.flag, action="store_true", help=sw.help)
     ap.add_argument("--save", default=None, metavar="PATH", help="write a checkpoint here after the last update")
     ap.add_argument("--data", default=None, help="'lobster' to load world_config.dataPath (else synthetic)")
     a = ap.parse_args(argv)
@@ -870,22 +794,9 @@ def main(argv=None) -> None:
             c.update({k: v for k, v in yaml.safe_load(f).items() if k in c})
     if a.envs:
         c["NUM_ENVS"] = a.envs
-    if a.fused_gru:
-        c["FUSED_GRU"] = True
-    if a.fused_policy:
-        c["FUSED_POLICY"] = True
-    if a.fused_loss:
-        c["FUSED_LOSS"] = True
-    if a.fused_opt:
-        c["FUSED_OPT"] = True
-    if a.grouped_scan:
-        c["GROUPED_SCAN"] = True
-    if a.fused_wgrad:
-        c["FUSED_WGRAD"] = True
-    if a.fused_wgrad_wide:
-        c["FUSED_WGRAD_WIDE"] = True
-    if a.calc_eval:
-        c["CALC_EVAL"] = True
+    for sw in SWITCHES:
+        if getattr(a, sw.key.lower()):
+            c[sw.key] = True
     cfg = (load_config_from_file(a.env_config) if a.env_config.endswith((".json", ".yaml"))
            else builtin_config(a.env_config))
     env = MARLEnv(None, cfg, data=a.data, return_info=False, persistent_outputs=True)

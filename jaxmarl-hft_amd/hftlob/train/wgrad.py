@@ -96,9 +96,13 @@ def _rows(t: torch.Tensor) -> torch.Tensor:
     return aligned(t.reshape(-1, t.shape[-1]).contiguous())
 
 
-class _NarrowLinear(torch.autograd.Function):
+class _Linear(torch.autograd.Function):
+    """``F.linear(x, w, b)`` whose weight and bias gradients are ``wgrad(d_y rows [N, out], x rows [N, in],
+    need_b) -> (d_w [out, in], d_b or None)``; the forward and the data gradient are torch's own."""
+
     @staticmethod
-    def forward(ctx, x, w, b):
+    def forward(ctx, wgrad, x, w, b):
+        ctx.wgrad = wgrad
         ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
         return F.linear(x, w, b)
@@ -106,18 +110,27 @@ class _NarrowLinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_y):
         x, w = ctx.saved_tensors
-        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        need_x, need_w, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.has_bias and ctx.needs_input_grad[3]
         # torch's own data gradient of the layer: the rows folded to 2-D, one mm
         d_x = d_y.reshape(-1, d_y.shape[-1]).mm(w).view(x.shape) if need_x else None
         d_w = d_b = None
         if need_w or need_b:
-            out_f, in_f = w.shape
-            if 1 <= out_f <= MAX_P and in_f in SUPPORTED_Q:   # narrow output (and a layer narrow on both sides)
-                d_w, d_b, _ = xty(_rows(d_y), _rows(x), want_sum_a=bool(need_b))
-            else:                                             # narrow input
-                C, _, d_b = xty(_rows(x), _rows(d_y), want_sum_b=bool(need_b))
-                d_w = C.t().contiguous()
-        return d_x, (d_w if need_w else None), (d_b if need_b else None)
+            d_w, d_b = ctx.wgrad(_rows(d_y), _rows(x), bool(need_b))
+        return None, d_x, (d_w if need_w else None), (d_b if need_b else None)
+
+
+def _narrow_wgrad(d_y, x, need_b):
+    """``_Linear``'s wgrad for a narrow layer: one ``xty`` call, the narrow side as its A."""
+    if 1 <= d_y.shape[1] <= MAX_P and x.shape[1] in SUPPORTED_Q:   # narrow output (and a layer narrow on both sides)
+        d_w, d_b, _ = xty(d_y, x, want_sum_a=need_b)
+        return d_w, d_b
+    C, _, d_b = xty(x, d_y, want_sum_b=need_b)                     # narrow input
+    return C.t().contiguous(), d_b
+
+
+def _wide_wgrad(d_y, x, need_b):
+    """``_Linear``'s wgrad for a wide layer: one ``xty_wide`` call."""
+    return xty_wide([d_y], x, want_sum_a=need_b)
 
 
 def narrow_linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -127,7 +140,7 @@ def narrow_linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = 
     if not narrow_linear_supported(w.shape[1], w.shape[0]):
         raise ValueError(f"narrow_linear: a layer of {w.shape[1]} -> {w.shape[0]} is not supported (one side in "
                          f"1..{MAX_P}, the other in {list(SUPPORTED_Q)})")
-    return _NarrowLinear.apply(x, w, b)
+    return _Linear.apply(_narrow_wgrad, x, w, b)
 
 
 # ------------------------------------------------------------------ the wide layers
@@ -221,25 +234,6 @@ def xty_wide(a_blocks, B: torch.Tensor, head: Optional[torch.Tensor] = None, shi
     return C, sa
 
 
-class _WideLinear(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w, b):
-        ctx.save_for_backward(x, w)
-        ctx.has_bias = b is not None
-        return F.linear(x, w, b)
-
-    @staticmethod
-    def backward(ctx, d_y):
-        x, w = ctx.saved_tensors
-        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        # torch's own data gradient of the layer: the rows folded to 2-D, one mm
-        d_x = d_y.reshape(-1, d_y.shape[-1]).mm(w).view(x.shape) if need_x else None
-        d_w = d_b = None
-        if need_w or need_b:
-            d_w, d_b = xty_wide([_rows(d_y)], _rows(x), want_sum_a=bool(need_b))
-        return d_x, (d_w if need_w else None), (d_b if need_b else None)
-
-
 def wide_linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``F.linear(x, w, b)`` for a layer that ``wide_linear_supported`` accepts: the same forward and data
     gradient (``d_y @ w``, only when x needs one), bit for bit; d_w and d_b from one ``xty_wide`` call over
@@ -247,4 +241,4 @@ def wide_linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = No
     if not wide_linear_supported(w.shape[1], w.shape[0]):
         raise ValueError(f"wide_linear: a layer of {w.shape[1]} -> {w.shape[0]} is not supported (inputs in "
                          f"{list(SUPPORTED_Q)}, outputs a multiple of 64 up to {WIDE_MAX_P})")
-    return _WideLinear.apply(x, w, b)
+    return _Linear.apply(_wide_wgrad, x, w, b)

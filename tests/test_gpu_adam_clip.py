@@ -420,7 +420,9 @@ def test_trainer_graphs_on_and_off_give_the_same_bits_with_the_switch():
         runs.append(tr)
     torch.cuda.synchronize()
     eager, graph = runs
-    assert graph.graphs and not eager.graphs and all(st["graph"] is not None for st in graph._st)
+    assert graph.graphs and not eager.graphs
+    assert [s["types"] for s in graph._steps] == [[i] for i in range(graph.n_types)]   # every type's own step
+    assert all(isinstance(s["graph"], torch.cuda.CUDAGraph) for s in graph._steps)
     for i in range(eager.n_types):
         for (name, p), q in zip(eager.nets[i].named_parameters(), graph.nets[i].parameters()):
             assert torch.equal(p, q), f"type {i}: {name}"

@@ -291,16 +291,38 @@ def config(cfg, **kw):
                             FUSED_LOSS=True, FUSED_OPT=True, NUM_AGENTS_PER_TYPE=cfg.number_of_agents_per_type, **kw)
 
 
-def run_pair(name, graphs, updates):
+def run_pair(name, graphs, updates, monkeypatch):
+    """A trainer without and one with the switch, ``updates`` updates each.  Counts the Python calls of the two
+    scans: every minibatch step of the plain trainer is one ``gru_scan`` of its type's net, every one of the joint
+    trainer one ``gru_scan_grouped`` of all the nets, and neither trainer calls the other's."""
     env, cfg = make_env(name)
+    calls = {"gru_scan": 0, "gru_scan_grouped": 0}
+
+    def counted(fn, real):
+        def wrapper(*a, **k):
+            calls[fn] += 1
+            return real(*a, **k)
+        return wrapper
+
+    for fn in calls:
+        monkeypatch.setattr(I, fn, counted(fn, getattr(I, fn)))
+    # a step group's Python runs per update: each of its 2 x 2 steps when eager; under graphs the two warm-ups and
+    # the capture, all in the first update, and then replays, which call no Python: the counts stop growing
+    runs_per_update = ([3] + [0] * (updates - 1)) if graphs else [4] * updates
     runs = []
     for grouped_scan in (False, True):
         tr = I.IPPOTrainer(env, config(cfg, CUDA_GRAPHS=graphs, GROUPED_SCAN=grouped_scan))
         assert tr.grouped_scan is grouped_scan and tr.graphs is graphs
-        losses = []
+        losses, counts = [], []
         for _ in range(updates):
+            before = dict(calls)
             m = tr.update()
+            counts.append(tuple(calls[fn] - before[fn] for fn in ("gru_scan", "gru_scan_grouped")))
             losses.append([{k: v.clone() for k, v in d.items()} for d in m["loss"]])
+        if grouped_scan:
+            assert counts == [(0, k) for k in runs_per_update], counts
+        else:
+            assert counts == [(tr.n_types * k, 0) for k in runs_per_update], counts
         runs.append((tr, losses))
     torch.cuda.synchronize()
     return runs
@@ -325,22 +347,23 @@ def assert_same_training(plain, joint, updates):
 
 
 @pytest.mark.parametrize("graphs", [False, True])
-def test_trainer_with_and_without_the_switch_two_types(graphs):
+def test_trainer_with_and_without_the_switch_two_types(graphs, monkeypatch):
     """Four updates of 2 x 2 minibatch steps; with graphs the joint step is warmed up, captured and replayed."""
-    plain, joint = run_pair("2_player_fq_fqc", graphs, 4)
+    plain, joint = run_pair("2_player_fq_fqc", graphs, 4, monkeypatch)
     assert_same_training(plain, joint, 4)
     tr = joint[0]
     assert all(n.fused for n in tr.nets)
     if graphs:
-        assert isinstance(tr._joint["graph"], torch.cuda.CUDAGraph)
-        assert all(st["graph"] is None for st in tr._st)               # (and no per-type step was captured)
-        assert all(isinstance(st["graph"], torch.cuda.CUDAGraph) for st in plain[0]._st)
+        assert [s["types"] for s in tr._steps] == [list(range(tr.n_types))]   # (one joint step and no per-type one)
+        assert isinstance(tr._steps[0]["graph"], torch.cuda.CUDAGraph)
+        assert [s["types"] for s in plain[0]._steps] == [[i] for i in range(plain[0].n_types)]
+        assert all(isinstance(s["graph"], torch.cuda.CUDAGraph) for s in plain[0]._steps)
     else:
-        assert tr._joint["graph"] is None
+        assert [s["graph"] for s in tr._steps] == [None]
 
 
-def test_trainer_with_and_without_the_switch_three_types():
-    plain, joint = run_pair("3_player_fq_fqc_dir", False, 2)
+def test_trainer_with_and_without_the_switch_three_types(monkeypatch):
+    plain, joint = run_pair("3_player_fq_fqc_dir", False, 2, monkeypatch)
     assert joint[0].n_types == 3
     assert_same_training(plain, joint, 2)
 
@@ -349,7 +372,8 @@ def test_restored_trainer_goes_on_with_the_switch(tmp_path):
     env, cfg = make_env("2_player_fq_fqc")
     src = I.IPPOTrainer(env, config(cfg, CUDA_GRAPHS=True, GROUPED_SCAN=True))
     src.update()
-    assert src._joint["graph"] is not None
+    assert [s["types"] for s in src._steps] == [list(range(src.n_types))]
+    assert isinstance(src._steps[0]["graph"], torch.cuda.CUDAGraph)
     path = str(tmp_path / "ck.pt")
     src.save_checkpoint(path)
     ck = torch.load(path, map_location="cpu", weights_only=False)
@@ -357,12 +381,13 @@ def test_restored_trainer_goes_on_with_the_switch(tmp_path):
     dst = I.IPPOTrainer(env, config(cfg, CUDA_GRAPHS=True, GROUPED_SCAN=True, SEED=3))
     dst.update()
     dst.load_checkpoint(path)
-    assert dst._joint["graph"] is None and dst._joint["warm"] == 0       # dropped with the per-type ones
+    assert [s["types"] for s in dst._steps] == [list(range(dst.n_types))]
+    assert dst._steps[0]["graph"] is None and dst._steps[0]["warm"] == 0   # dropped: captured again at the next update
     for i in range(src.n_types):
         for p, q in zip(src.nets[i].parameters(), dst.nets[i].parameters()):
             assert torch.equal(p, q)
     m = dst.update()
     assert all(np.isfinite(float(v)) for d in m["loss"] for v in d.values())
-    assert dst._joint["graph"] is not None and dst.opt_count == [8, 8]
+    assert isinstance(dst._steps[0]["graph"], torch.cuda.CUDAGraph) and dst.opt_count == [8, 8]
     for i in range(dst.n_types):
         assert all(float(dst.opts[i].state[p]["step"]) == 8.0 for p in dst.nets[i].parameters())

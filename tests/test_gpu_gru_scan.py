@@ -220,7 +220,7 @@ def test_module_forward_fused_matches_loop():
 
 def test_fused_step_captures_and_replays_bit_for_bit():
     """forward + loss + backward with the fused scan inside one torch.cuda.graph (warm-up on a side
-    stream, IPPOTrainer._minibatch's pattern); two replays with new input contents equal the eager
+    stream, IPPOTrainer._run_step's pattern); two replays with new input contents equal the eager
     fused results bit for bit."""
     net, g = _net_and_batch(seed=3)
     net.fused = True
@@ -269,6 +269,7 @@ def test_trainer_updates_with_fused_gru_in_the_graph():
         m = tr.update()
         for d in m["loss"]:
             assert all(np.isfinite(float(v)) for v in d.values())
-    assert all(isinstance(st["graph"], torch.cuda.CUDAGraph) for st in tr._st)
+    assert [s["types"] for s in tr._steps] == [[i] for i in range(tr.n_types)]   # every type's own step
+    assert all(isinstance(s["graph"], torch.cuda.CUDAGraph) for s in tr._steps)
     with pytest.raises(ValueError, match="FUSED_GRU needs GRU_HIDDEN_DIM"):
         I.IPPOTrainer(env, I.default_config(NUM_ENVS=64, NUM_STEPS=8, GRU_HIDDEN_DIM=32, FUSED_GRU=True))

@@ -96,7 +96,8 @@ def test_updates_with_everything_fused_in_graphs(env):
         for d in m["loss"]:
             assert all(np.isfinite(float(v)) for v in d.values())
     assert isinstance(tr._roll, torch.cuda.CUDAGraph)   # the rollout did not fall back to eager
-    assert all(isinstance(st["graph"], torch.cuda.CUDAGraph) for st in tr._st)
+    assert [s["types"] for s in tr._steps] == [[i] for i in range(tr.n_types)]   # every type's own step
+    assert all(isinstance(s["graph"], torch.cuda.CUDAGraph) for s in tr._steps)
 
 
 def test_unsupported_size_raises(env):

@@ -331,4 +331,5 @@ def test_trainer_in_graphs_with_the_switch():
         m = tr.update()
         assert all(np.isfinite(float(v)) for d in m["loss"] for v in d.values())
         assert all(np.isfinite(float(r)) for r in m["avg_reward"])
-    assert all(st["graph"] is not None for st in tr._st)
+    assert [s["types"] for s in tr._steps] == [[i] for i in range(tr.n_types)]   # every type's own step
+    assert all(isinstance(s["graph"], torch.cuda.CUDAGraph) for s in tr._steps)

@@ -108,10 +108,10 @@ def test_learner_on_device_matches_numpy():
         # one minibatch step through the trainer (fresh Adam state) vs float64 on the CPU
         ref = copy.deepcopy(net).double().cpu()
         tr.opts[i] = torch.optim.Adam(net.parameters(), lr=c["LR"][i], eps=1e-5)
-        st = tr._static(i, n, MB)
+        st = tr._st[i]
         st["h0"].copy_(h0[i]); st["adv"].copy_(adv); st["tgt"].copy_(tgt); st["idx"].copy_(idx)
         tr.opts[i].zero_grad(set_to_none=True)
-        tr._mb_step(i)
+        tr._step([i])
         cpu = lambda x: x.detach().cpu()  # noqa: E731
         lg, vv = ref(cpu(h0[i][idx]).double(), cpu(b.obs[:, idx]).double(), cpu(b.done[:, idx]))
         loss = I.ppo_loss(lg, vv, cpu(b.action[:, idx]), cpu(b.value[:, idx]).double(), cpu(b.log_prob[:, idx]).double(),

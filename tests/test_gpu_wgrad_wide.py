@@ -326,7 +326,7 @@ def test_module_with_the_switch_matches_the_module_without(fused):
 @pytest.mark.parametrize("fused", [False, True], ids=["loop", "fused_scan"])
 def test_step_with_the_switch_captures_and_replays_bit_for_bit(fused):
     """forward + loss + backward with fused_wgrad_wide inside one torch.cuda.graph (warm-up on a side stream,
-    IPPOTrainer._minibatch's pattern); two replays with new input contents equal the eager results bit for
+    IPPOTrainer._run_step's pattern); two replays with new input contents equal the eager results bit for
     bit."""
     torch.manual_seed(3)
     net = I.ActorCriticRNN(12, 13, 64, 64).cuda()
@@ -388,9 +388,11 @@ def test_trainer_updates_with_every_switch_per_type_and_grouped():
             m = tr.update()
             assert all(np.isfinite(float(v)) for d in m["loss"] for v in d.values())
         if grouped:
-            assert isinstance(tr._joint["graph"], torch.cuda.CUDAGraph)
+            assert [s["types"] for s in tr._steps] == [list(range(tr.n_types))]   # the one joint step
+            assert isinstance(tr._steps[0]["graph"], torch.cuda.CUDAGraph)
         else:
-            assert all(isinstance(st["graph"], torch.cuda.CUDAGraph) for st in tr._st)
+            assert [s["types"] for s in tr._steps] == [[i] for i in range(tr.n_types)]   # every type's own step
+            assert all(isinstance(s["graph"], torch.cuda.CUDAGraph) for s in tr._steps)
         runs.append(tr)
     torch.cuda.synchronize()
     a, b = runs   # the operator is the same per net either way: the same training, bit for bit

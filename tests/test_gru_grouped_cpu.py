@@ -155,14 +155,14 @@ def _run(grouped, monkeypatch):
     calls = []
     real = I.ActorCriticRNN.forward_grouped
     monkeypatch.setattr(I.ActorCriticRNN, "forward_grouped",
-                        staticmethod(lambda *a, **k: (calls.append(1), real(*a, **k))[1]))
+                        staticmethod(lambda nets, *a, **k: (calls.append(len(nets)), real(nets, *a, **k))[1]))
     tr = I.IPPOTrainer(TwoTypeEnv(), I.default_config(**KW, GROUPED_SCAN=grouped))
     assert tr.grouped_scan is grouped and all(c for c in tr.c["ANNEAL_LR"])
     losses, per_update = [], []
     for _ in range(3):
         before = len(calls)
         m = tr.update()
-        per_update.append(len(calls) - before)
+        per_update.append(calls[before:])   # the number of nets of every forward_grouped call of this update
         losses.append([{k: v.clone() for k, v in d.items()} for d in m["loss"]])
         assert len(m["avg_reward"]) == 2
     return tr, losses, per_update
@@ -171,8 +171,10 @@ def _run(grouped, monkeypatch):
 def test_joint_update_equals_the_per_type_update_bit_for_bit(monkeypatch):
     plain, l0, n0 = _run(False, monkeypatch)
     joint, l1, n1 = _run(True, monkeypatch)
-    assert n0 == [0, 0, 0]
-    assert n1 == [KW["UPDATE_EPOCHS"] * KW["NUM_MINIBATCHES"]] * 3   # the joint path ran, once per minibatch step
+    steps = KW["UPDATE_EPOCHS"] * KW["NUM_MINIBATCHES"]
+    # (the last-value step of an update is net.step: it does not go through forward_grouped)
+    assert n0 == [[1] * (plain.n_types * steps)] * 3   # every type's minibatch steps on their own, one net each
+    assert n1 == [[joint.n_types] * steps] * 3         # the lockstep path: one call per step, all the nets
     assert plain.opt_count == joint.opt_count == [12, 12]
     assert torch.equal(plain.gen.get_state(), joint.gen.get_state())
     for a, b in zip(plain.nets, joint.nets):

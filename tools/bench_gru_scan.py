@@ -155,7 +155,7 @@ def main(argv=None):
                 hseq.backward(d_hseq)
             return hseq
 
-        side = torch.cuda.Stream(dev)   # warm-up on a side stream (IPPOTrainer._minibatch's pattern)
+        side = torch.cuda.Stream(dev)   # warm-up on a side stream (IPPOTrainer._run_step's pattern)
         side.wait_stream(stream)
         with torch.cuda.stream(side):
             for _ in range(2):

@@ -71,7 +71,7 @@ def main(argv=None):
             out[0].backward()
             return torch.stack([t.detach() for t in out])
 
-        side = torch.cuda.Stream(dev)   # warm-up on a side stream (IPPOTrainer._minibatch's pattern)
+        side = torch.cuda.Stream(dev)   # warm-up on a side stream (IPPOTrainer._run_step's pattern)
         side.wait_stream(stream)
         with torch.cuda.stream(side):
             for _ in range(2):
