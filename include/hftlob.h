@@ -43,6 +43,8 @@
  *                           pi.sample / log_prob (:590-600), for a batch of actors.
  *   hftlob_policy_step_multi <- the same step with :80-100 MultiActionOutputIndependant and :259-281
  *                           MultiCategorical: one categorical head per word of a MultiDiscrete space.
+ *   hftlob_policy_step_grouped <- the same steps of several independent nets (IPPO's one net per agent
+ *                           type; the runs of a sweep, :1274 wandb.agent) as one launch.
  */
 #ifndef HFTLOB_H
 #define HFTLOB_H
@@ -678,6 +680,38 @@ int hftlob_policy_step_multi(int B, int D, int FC, int H, int K, const int* nvec
                              int mode, const uint32_t* keys /*[K][2], device; mode 0 only*/,
                              int32_t* action /*[B][K]*/, float* log_prob /*[B]*/, float* value /*[B]*/,
                              float* logits /*[B][S] or NULL*/, void* stream);
+
+/* The policy step of up to HFTLOB_POLICY_MAX_GROUPS independent nets ("groups": the agent types of an IPPO
+ * run, or of several runs trained side by side) as one launch.  The groups share FC, H and mode; each has
+ * its own B, D, heads (K of them, nvec[0 .. K-1] wide), weights and arrays, with the layouts and meanings
+ * of hftlob_policy_step_multi: keys [K][2], action [B][K], logits [B][S] or NULL.  groups is a host array
+ * that is read during the call only: the table travels by value in the kernel arguments, so the call
+ * makes no copy to the device and can be captured in a graph.  A workgroup owns one 16-row tile of one
+ * group; tiles never straddle groups, each group's tiles start at its row 0, and the grid is the sum of
+ * the groups' tile counts.  The per-tile arithmetic is that of the single operators (one device function
+ * serves all three), so every group's h_out, action, log_prob, value and logits equal bit for bit what
+ * hftlob_policy_step_multi gives for that group alone (and so, for a group of one head, what
+ * hftlob_policy_step gives with A = nvec[0] and key = keys), in both modes, whatever the other groups and
+ * their order.  Per group h_out may be h_in; the outputs of different groups must not alias.  Rows past a
+ * group's B are neither read out of bounds nor written.
+ * HFTLOB_ESHAPE: n_groups outside 1..HFTLOB_POLICY_MAX_GROUPS; HFTLOB_ENULL: groups is NULL; then per
+ * group, in group order, the checks of hftlob_policy_step_multi in their order and with its codes, the
+ * message (hftlob_last_error) naming the group as "group g". */
+#define HFTLOB_POLICY_MAX_GROUPS 8
+typedef struct {
+    int B, D, K;
+    int nvec[4];
+    hftlob_policy_weights w;
+    const float* obs;
+    const uint8_t* done;
+    const float* h_in;
+    float* h_out;
+    const uint32_t* keys;
+    int32_t* action;
+    float *log_prob, *value, *logits /* or NULL */;
+} hftlob_policy_group;
+int hftlob_policy_step_grouped(int FC, int H, int n_groups, const hftlob_policy_group* groups /*[host]*/,
+                               int mode, void* stream);
 
 /* Generalised advantage estimation of the learner (_calculate_gae, ippo_rnn_JAXMARL.py:668-690) as one
  * launch, float32.  reward, value, adv, targets [T][n]; done bytes [T][n] (non-zero: the step ended the

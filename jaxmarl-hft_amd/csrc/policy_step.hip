@@ -1,5 +1,6 @@
 // Fused recurrent policy step for IPPO rollouts and policy evaluation (include/hftlob.h:
-// hftlob_policy_step, and hftlob_policy_step_multi for MultiDiscrete action spaces), gfx950.
+// hftlob_policy_step, hftlob_policy_step_multi for MultiDiscrete action spaces, and
+// hftlob_policy_step_grouped, which steps several independent nets' batches in one launch), gfx950.
 //
 // One ActorCriticRNN step (jaxrl/MARL/ippo_rnn_JAXMARL.py:53-78, 183-256) for a batch of actors as
 // one launch: embedding, GRU cell, critic and actor heads, softmax, the sample (or the argmax) and
@@ -33,6 +34,7 @@
 // its wait, and a sched_barrier keeps the loads where they are issued.  A stage's first chunks are
 // requested before the previous stage's epilogue and barrier.
 #include <stdint.h>
+#include <stdio.h>
 
 #include "hftlob_draw.h"  // threefry_bits, gumbel_from_bits
 #include "hftlob_tile.h"  // f32x4, ld4 / splat, sigmoidf_, TILE and the MFMA operand maps
@@ -136,15 +138,59 @@ __device__ __forceinline__ void head_pick(float x, float sc, bool live_a, int l,
     lp = xa - mx - logf(sum);
 }
 
+// A batch as the kernel takes it: the operators' arguments (hftlob_policy_group's fields) with the heads'
+// offsets worked out
+struct Group {
+    int B, D;
+    Heads hd;
+    hftlob_policy_weights W;
+    const float* obs;
+    const uint8_t* done;
+    const float* h_in;
+    float* h_out;
+    const u32* key;
+    int32_t* action;
+    float *log_prob, *value, *logits;
+};
+
+// The batches of a launch, by value in the kernel arguments, as gru_scan.hip's table travels: the call
+// needs no copy to the device and can be captured in a graph.  first[g] is group g's first tile,
+// first[MG] the grid; the unused entries repeat group 0 and have no tiles.  MG is 1 for the single-batch
+// operators (no lookup: the table is the batch) and HFTLOB_POLICY_MAX_GROUPS for hftlob_policy_step_grouped
+template <int MG>
+struct GroupTable {
+    Group g[MG];
+    int first[MG + 1];
+};
+constexpr int MAXG = HFTLOB_POLICY_MAX_GROUPS;
+static_assert(sizeof(GroupTable<MAXG>) <= 4096, "the group table travels in the kernel arguments");
+
 // The step of a tile: hd.K <= NHD heads, key [K][2], action [B][K], logits [B][S].  NHD is the number of
-// column blocks the logits stage runs on the one A operand in wave 0: 1 for hftlob_policy_step (one
-// head of A logits, so action [B] and logits [B][A]), MAXK for hftlob_policy_step_multi
-template <int H, int FC, int NHD>
-__global__ __launch_bounds__((Shape<H, FC>::NT)) void k_policy_step(
-    int B, int D, Heads hd, hftlob_policy_weights W, const float* __restrict__ obs,
-    const uint8_t* __restrict__ done, const float* h_in, float* h_out, int mode, const u32* __restrict__ key,
-    int32_t* __restrict__ action, float* __restrict__ log_prob, float* __restrict__ value,
-    float* __restrict__ logits) {
+// column blocks the logits stage runs on the one A operand in wave 0: 1 where every batch has one head
+// (hftlob_policy_step: action [B] and logits [B][A]), MAXK otherwise (hftlob_policy_step_multi).
+// One kernel serves the single-batch operators and the grouped launch.  A workgroup of the grouped launch
+// finds its group from blockIdx once: the index is wave-uniform, so the group's sizes and pointers are
+// scalar loads from the kernarg segment, as the single batch's are.  The body stays in the kernel: as a
+// __device__ function of a tile, inlined into two kernels, the same text compiles to a different schedule
+// that spills at H = 256 ("The grouped policy step")
+template <int H, int FC, int NHD, int MG>
+__global__ __launch_bounds__((Shape<H, FC>::NT)) void k_policy_step(const GroupTable<MG> tb, int mode) {
+    int grp = 0;
+    if constexpr (MG > 1)
+        while ((int)blockIdx.x >= tb.first[grp + 1]) ++grp;  // (the grid is first[MG] workgroups: grp stays below MG)
+    const Group& x = tb.g[grp];
+    const int B = x.B, D = x.D;
+    const Heads& hd = x.hd;
+    const hftlob_policy_weights& W = x.W;
+    const float* __restrict__ obs = x.obs;
+    const uint8_t* __restrict__ done = x.done;
+    const float* h_in = x.h_in;
+    float* h_out = x.h_out;
+    const u32* __restrict__ key = x.key;
+    int32_t* __restrict__ action = x.action;
+    float* __restrict__ log_prob = x.log_prob;
+    float* __restrict__ value = x.value;
+    float* __restrict__ logits = x.logits;
     typedef Shape<H, FC> Sh;
     constexpr int CB = Sh::CB, NW = Sh::NW, NT = Sh::NT, NBE = Sh::NBE, NBH = Sh::NBH;
     constexpr int SX = FC + 4, SH = H + 4, NG = 3 * CB;
@@ -153,7 +199,7 @@ __global__ __launch_bounds__((Shape<H, FC>::NT)) void k_policy_step(
     __shared__ __attribute__((aligned(16))) float bp[TILE * SH];  // h_prev, then relu(actor1)
     __shared__ __attribute__((aligned(16))) float bh[TILE * SH];  // obs, then h
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, li = l & 15, q = l >> 4;
-    const int b0 = blockIdx.x * TILE;
+    const int b0 = ((int)blockIdx.x - (MG > 1 ? tb.first[grp] : 0)) * TILE;
 
     // the gates' W_ih rows and the embedding's B operands, requested before anything waits
     int col[CB];
@@ -350,56 +396,87 @@ bool misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
     HFTLOB_POLICY_CASE(256, 128)  \
     HFTLOB_POLICY_CASE(256, 256)
 
-// Both operators' checks and launch, with NHD logits blocks.  The checks run in the order they always
-// have: the sizes, then head_check (the operator's own check of K and nv, which are read only after
-// it passes), then the mode, the pointers and the alignment
+// The text in front of a check's message: the operator, and for a grouped call the group (else -1)
+struct Who {
+    const char* op;
+    int group;
+};
+
+int fail_at(Who who, int code, const char* text) {
+    char msg[200];
+    if (who.group < 0) snprintf(msg, sizeof msg, "%s: %s", who.op, text);
+    else snprintf(msg, sizeof msg, "%s: group %d: %s", who.op, who.group, text);
+    return hftlob_fail(code, msg);
+}
+
+// Every operator's checks of one batch, and its heads.  The checks run in the order they always have:
+// the sizes, then head_check (the operator's own check of K and nv, which are read only after it
+// passes), then the mode, the pointers and the alignment
+template <class HeadCheck>
+int policy_check(Who who, int B, int D, int FC, int H, int K, const int* nv, HeadCheck head_check,
+                 const hftlob_policy_weights* w, const float* obs, const uint8_t* done, const float* h_in,
+                 const float* h_out, int mode, const uint32_t* key, const int32_t* action, const float* log_prob,
+                 const float* value, Heads* hd) {
+    if (B < 1) return fail_at(who, HFTLOB_ESHAPE, "B must be >= 1");
+    if (!size_ok(H)) return fail_at(who, HFTLOB_ESHAPE, "H must be 64, 128 or 256");
+    if (!size_ok(FC)) return fail_at(who, HFTLOB_ESHAPE, "FC must be 64, 128 or 256");
+    if (D < 1 || D > DMAX) return fail_at(who, HFTLOB_ESHAPE, "D must be in 1..64");
+    if (int rc = head_check()) return rc;
+    if (mode != 0 && mode != 1) return fail_at(who, HFTLOB_EINVAL, "mode must be 0 (sample) or 1 (argmax)");
+    if (!w) return fail_at(who, HFTLOB_ENULL, "w (the weight struct) is NULL");
+    if (!w->w_embed || !w->b_embed || !w->w_ih || !w->b_ih || !w->w_hh || !w->b_hh || !w->w_c1 || !w->b_c1 ||
+        !w->w_c2 || !w->b_c2 || !w->w_a1 || !w->b_a1 || !w->w_a2 || !w->b_a2)
+        return fail_at(who, HFTLOB_ENULL, "a pointer of the weight struct w is NULL");
+    if (!obs) return fail_at(who, HFTLOB_ENULL, "obs is NULL");
+    if (!done) return fail_at(who, HFTLOB_ENULL, "done is NULL");
+    if (!h_in) return fail_at(who, HFTLOB_ENULL, "h_in is NULL");
+    if (!h_out) return fail_at(who, HFTLOB_ENULL, "h_out is NULL");
+    if (mode == 0 && !key) return fail_at(who, HFTLOB_ENULL, "key is NULL (mode 0 samples from it)");
+    if (!action) return fail_at(who, HFTLOB_ENULL, "action is NULL");
+    if (!log_prob) return fail_at(who, HFTLOB_ENULL, "log_prob is NULL");
+    if (!value) return fail_at(who, HFTLOB_ENULL, "value is NULL");
+    if (misaligned(w->w_ih) || misaligned(w->w_hh) || misaligned(w->w_c1) || misaligned(w->w_a1) || misaligned(w->w_a2))
+        return fail_at(who, HFTLOB_EINVAL, "w_ih, w_hh, w_c1, w_a1 and w_a2 must be 16-byte aligned");
+    hd->K = K;
+    hd->S = 0;
+    for (int k = 0; k < K; ++k) {
+        hd->nv[k] = nv[k];
+        hd->off[k] = hd->S;
+        hd->S += nv[k];
+    }
+    for (int k = K; k < MAXK; ++k) {  // the entries past K repeat head K - 1
+        hd->nv[k] = hd->nv[K - 1];
+        hd->off[k] = hd->off[K - 1];
+    }
+    return HFTLOB_OK;
+}
+
+// The launch of a checked table, with NHD logits blocks
+template <int NHD, int MG>
+int table_launch(int FC, int H, const GroupTable<MG>& tb, int mode, void* stream) {
+    const dim3 grid((unsigned)tb.first[MG]);
+    hipStream_t s = (hipStream_t)stream;
+#define HFTLOB_POLICY_CASE(h, fc) \
+    if (H == h && FC == fc) k_policy_step<h, fc, NHD, MG><<<grid, Shape<h, fc>::NT, 0, s>>>(tb, mode);
+    HFTLOB_POLICY_CASES
+#undef HFTLOB_POLICY_CASE
+    return launch_status();
+}
+
+// The two single-batch operators' checks and launch, with NHD logits blocks
 template <int NHD, class HeadCheck>
 int policy_launch(int B, int D, int FC, int H, int K, const int* nv, HeadCheck head_check,
                   const hftlob_policy_weights* w, const float* obs, const uint8_t* done, const float* h_in, float* h_out,
                   int mode, const uint32_t* key, int32_t* action, float* log_prob, float* value, float* logits,
                   void* stream) {
-    if (B < 1) return hftlob_fail(HFTLOB_ESHAPE, "policy_step: B must be >= 1");
-    if (!size_ok(H)) return hftlob_fail(HFTLOB_ESHAPE, "policy_step: H must be 64, 128 or 256");
-    if (!size_ok(FC)) return hftlob_fail(HFTLOB_ESHAPE, "policy_step: FC must be 64, 128 or 256");
-    if (D < 1 || D > DMAX) return hftlob_fail(HFTLOB_ESHAPE, "policy_step: D must be in 1..64");
-    if (int rc = head_check()) return rc;
-    if (mode != 0 && mode != 1) return hftlob_fail(HFTLOB_EINVAL, "policy_step: mode must be 0 (sample) or 1 (argmax)");
-    if (!w) return hftlob_fail(HFTLOB_ENULL, "policy_step: w (the weight struct) is NULL");
-    if (!w->w_embed || !w->b_embed || !w->w_ih || !w->b_ih || !w->w_hh || !w->b_hh || !w->w_c1 || !w->b_c1 ||
-        !w->w_c2 || !w->b_c2 || !w->w_a1 || !w->b_a1 || !w->w_a2 || !w->b_a2)
-        return hftlob_fail(HFTLOB_ENULL, "policy_step: a pointer of the weight struct w is NULL");
-    if (!obs) return hftlob_fail(HFTLOB_ENULL, "policy_step: obs is NULL");
-    if (!done) return hftlob_fail(HFTLOB_ENULL, "policy_step: done is NULL");
-    if (!h_in) return hftlob_fail(HFTLOB_ENULL, "policy_step: h_in is NULL");
-    if (!h_out) return hftlob_fail(HFTLOB_ENULL, "policy_step: h_out is NULL");
-    if (mode == 0 && !key) return hftlob_fail(HFTLOB_ENULL, "policy_step: key is NULL (mode 0 samples from it)");
-    if (!action) return hftlob_fail(HFTLOB_ENULL, "policy_step: action is NULL");
-    if (!log_prob) return hftlob_fail(HFTLOB_ENULL, "policy_step: log_prob is NULL");
-    if (!value) return hftlob_fail(HFTLOB_ENULL, "policy_step: value is NULL");
-    if (misaligned(w->w_ih) || misaligned(w->w_hh) || misaligned(w->w_c1) || misaligned(w->w_a1) || misaligned(w->w_a2))
-        return hftlob_fail(HFTLOB_EINVAL, "policy_step: w_ih, w_hh, w_c1, w_a1 and w_a2 must be 16-byte aligned");
     static_assert(NHD <= MAXK, "Heads holds MAXK entries");
     Heads hd;
-    hd.K = K;
-    hd.S = 0;
-    for (int k = 0; k < K; ++k) {
-        hd.nv[k] = nv[k];
-        hd.off[k] = hd.S;
-        hd.S += nv[k];
-    }
-    for (int k = K; k < MAXK; ++k) {  // the entries past K repeat head K - 1
-        hd.nv[k] = hd.nv[K - 1];
-        hd.off[k] = hd.off[K - 1];
-    }
-    const dim3 grid((unsigned)((B + TILE - 1) / TILE));
-    hipStream_t s = (hipStream_t)stream;
-#define HFTLOB_POLICY_CASE(h, fc)                                                                                     \
-    if (H == h && FC == fc)                                                                                           \
-        k_policy_step<h, fc, NHD><<<grid, Shape<h, fc>::NT, 0, s>>>(B, D, hd, *w, obs, done, h_in, h_out, mode, key,  \
-                                                                    action, log_prob, value, logits);
-    HFTLOB_POLICY_CASES
-#undef HFTLOB_POLICY_CASE
-    return launch_status();
+    if (const int rc = policy_check(Who{"policy_step", -1}, B, D, FC, H, K, nv, head_check, w, obs, done, h_in, h_out,
+                                    mode, key, action, log_prob, value, &hd))
+        return rc;
+    const GroupTable<1> tb{{Group{B, D, hd, *w, obs, done, h_in, h_out, key, action, log_prob, value, logits}},
+                           {0, (B + TILE - 1) / TILE}};
+    return table_launch<NHD>(FC, H, tb, mode, stream);
 }
 
 }  // namespace
@@ -428,4 +505,53 @@ extern "C" int hftlob_policy_step_multi(int B, int D, int FC, int H, int K, cons
     };
     return policy_launch<MAXK>(B, D, FC, H, K, nvec, head_check, w, obs, done, h_in, h_out, mode, keys, action, log_prob,
                                value, logits, stream);
+}
+
+extern "C" int hftlob_policy_step_grouped(int FC, int H, int n_groups, const hftlob_policy_group* groups, int mode,
+                                          void* stream) {
+    const Who all{"policy_step_grouped", -1};
+    if (n_groups < 1 || n_groups > MAXG) return fail_at(all, HFTLOB_ESHAPE, "n_groups must be in 1..8");
+    if (!groups) return fail_at(all, HFTLOB_ENULL, "groups is NULL");
+    if (!size_ok(H)) return fail_at(all, HFTLOB_ESHAPE, "H must be 64, 128 or 256");
+    if (!size_ok(FC)) return fail_at(all, HFTLOB_ESHAPE, "FC must be 64, 128 or 256");
+    GroupTable<MAXG> tb;
+    long long tiles = 0;
+    bool one_head = true;
+    for (int g = 0; g < n_groups; ++g) {
+        const hftlob_policy_group& x = groups[g];
+        const Who who{"policy_step_grouped", g};
+        const auto head_check = [&] {
+            if (x.K < 1 || x.K > MAXK) return fail_at(who, HFTLOB_ESHAPE, "K must be in 1..4");
+            for (int k = 0; k < x.K; ++k)
+                if (x.nvec[k] < 1 || x.nvec[k] > 16) return fail_at(who, HFTLOB_ESHAPE, "every nvec entry must be in 1..16");
+            return (int)HFTLOB_OK;
+        };
+        Group& t = tb.g[g];
+        if (const int rc = policy_check(who, x.B, x.D, FC, H, x.K, x.nvec, head_check, &x.w, x.obs, x.done, x.h_in,
+                                        x.h_out, mode, x.keys, x.action, x.log_prob, x.value, &t.hd))
+            return rc;
+        t.B = x.B;
+        t.D = x.D;
+        t.W = x.w;
+        t.obs = x.obs;
+        t.done = x.done;
+        t.h_in = x.h_in;
+        t.h_out = x.h_out;
+        t.key = x.keys;
+        t.action = x.action;
+        t.log_prob = x.log_prob;
+        t.value = x.value;
+        t.logits = x.logits;
+        tb.first[g] = (int)tiles;
+        tiles += (x.B + TILE - 1) / TILE;
+        if (tiles > INT32_MAX) return fail_at(all, HFTLOB_ESHAPE, "more than 2^31 - 1 tiles");
+        one_head = one_head && x.K == 1;
+    }
+    for (int g = n_groups; g < MAXG; ++g) {  // the unused entries repeat group 0 and have no tiles
+        tb.g[g] = tb.g[0];
+        tb.first[g] = (int)tiles;
+    }
+    tb.first[MAXG] = (int)tiles;
+    // one head everywhere: the single operator's one logits block, else the multi-head operator's MAXK
+    return one_head ? table_launch<1>(FC, H, tb, mode, stream) : table_launch<MAXK>(FC, H, tb, mode, stream);
 }

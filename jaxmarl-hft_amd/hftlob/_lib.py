@@ -41,6 +41,13 @@ class PolicyWeights(C.Structure):
                                           "w_c2", "b_c2", "w_a1", "b_a1", "w_a2", "b_a2")]
 
 
+class PolicyGroup(C.Structure):
+    """hftlob_policy_group (include/hftlob.h): one group of hftlob_policy_step_grouped."""
+    _fields_ = ([("B", C.c_int), ("D", C.c_int), ("K", C.c_int), ("nvec", C.c_int * 4), ("w", PolicyWeights)]
+                + [(k, C.c_void_p) for k in ("obs", "done", "h_in", "h_out", "keys", "action", "log_prob", "value",
+                                             "logits")])
+
+
 LIB_PATH = os.environ.get("HFTLOB_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhftlob.so")
 ABI_VERSION = 8
 EVAL_WORDS = 106  # HFTLOB_EVAL_WORDS: doubles per agent in hftlob_env_rollout_eval's stats (the table is in hftlob.h)
@@ -52,7 +59,7 @@ EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob
            "hftlob_env_lds_bytes", "hftlob_env_launch_info", "hftlob_env_baked_id", "hftlob_set_baked",
            "hftlob_sample_actions", "hftlob_split_keys", "hftlob_gru_scan_fwd", "hftlob_gru_scan_bwd",
            "hftlob_gru_scan_fwd_grouped", "hftlob_gru_scan_bwd_grouped",
-           "hftlob_policy_step", "hftlob_policy_step_multi", "hftlob_gae", "hftlob_ppo_loss",
+           "hftlob_policy_step", "hftlob_policy_step_multi", "hftlob_policy_step_grouped", "hftlob_gae", "hftlob_ppo_loss",
            "hftlob_adam_clip", "hftlob_xty", "hftlob_xty_workspace", "hftlob_xty_wide", "hftlob_xty_wide_workspace")
 
 _lib = None
@@ -128,6 +135,8 @@ def lib() -> C.CDLL:
     L.hftlob_policy_step_multi.argtypes = [i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(PolicyWeights), vp, vp,
                                            vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.hftlob_policy_step_multi.restype = i32
+    L.hftlob_policy_step_grouped.argtypes = [i32, i32, i32, C.POINTER(PolicyGroup), i32, vp]
+    L.hftlob_policy_step_grouped.restype = i32
     L.hftlob_gae.argtypes = [i32, i32, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp]
     L.hftlob_gae.restype = i32
     L.hftlob_ppo_loss.argtypes = [i32, i32, C.POINTER(i32), vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double,

@@ -526,7 +526,7 @@ def policy_entries(nets: Sequence, n_types: int) -> list:
 
 
 def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: bool = True,
-                    chunk: int = 64) -> EvalStats:
+                    chunk: int = 64, grouped: bool = False) -> EvalStats:
     """:func:`evaluate_fixed_actions` with recurrent policies in place of the fixed actions: ``nets``
     holds one entry per agent type, an ``ActorCriticRNN`` (``hftlob.train.ippo.load_policy``) or a
     fixed action (an int, or a list of one int), in any mix.  Every agent of a fixed type, and every
@@ -542,9 +542,11 @@ def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: boo
     only.  The env must be built with ``return_info=True``.
     An entry may also be a :class:`Uniform`: the type (a Discrete space of at most 32 actions) has no
     carry either, and its step is one :func:`draw_actions` launch under the type's policy key of the
-    step, the key a learned type would sample with; learned and fixed types are as without it."""
+    step, the key a learned type would sample with; learned and fixed types are as without it.
+    ``grouped``: the learned types' steps of a step are one launch (``train.policy.policy_step_grouped``: at
+    most 8 learned types of one FC_DIM_SIZE and GRU_HIDDEN_DIM), with the same statistics bit for bit."""
     from .env import split_keys
-    from .train.policy import GREEDY, SAMPLE, policy_step_net
+    from .train.policy import GREEDY, SAMPLE, policy_step_grouped, policy_step_grouped_supported, policy_step_net
     if n_envs < 1 or n_steps < 1 or chunk < 1:
         raise ValueError("n_envs, n_steps and chunk must be >= 1")
     if not getattr(env, "return_info", False):
@@ -552,6 +554,9 @@ def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: boo
     counts = list(env.multi_agent_config.number_of_agents_per_type)
     pols = policy_entries(nets, len(counts))
     learned = [i for i, p in enumerate(pols) if isinstance(p, torch.nn.Module)]
+    if grouped and learned and not policy_step_grouped_supported([pols[i] for i in learned]):
+        raise ValueError("evaluate_policy(grouped=True) needs at most 8 learned types of one FC_DIM_SIZE and "
+                         "GRU_HIDDEN_DIM, each within the fused policy step's sizes")
     drawn = [i for i, p in enumerate(pols) if isinstance(p, Uniform)]
     allowed = draw_masks(env, pols) if drawn else None
     part = bool(env.cfg_c.prng_partitionable)
@@ -579,8 +584,13 @@ def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: boo
         keys = split_keys(torch.cat(sub).contiguous(), n_envs, part)                       # [T, E, 2]
         pol = split_keys(torch.cat(act).contiguous(), len(pols), part)                     # [T, n_types, 2]
         for t in range(T):
-            for i in learned:
-                a = policy_step_net(pols[i], obs[i], done[i], h[i], mode, key=pol[t, i] if mode == SAMPLE else None)[1]
+            if grouped and learned:
+                outs = policy_step_grouped([pols[i] for i in learned], [obs[i] for i in learned],
+                                           [done[i] for i in learned], [h[i] for i in learned], mode,
+                                           keys=[pol[t, i] for i in learned] if mode == SAMPLE else None)
+            for j, i in enumerate(learned):
+                a = outs[j][1] if grouped else policy_step_net(pols[i], obs[i], done[i], h[i], mode,
+                                                               key=pol[t, i] if mode == SAMPLE else None)[1]
                 actions[i] = a.view(E, counts[i], *a.shape[1:])   # [E, n_t], or [E, n_t, K] of a MultiDiscrete type
             for i in drawn:
                 _draw_launch(n_act[i], env.action_spaces[i].n, allowed[i], pol[t, i], actions[i])

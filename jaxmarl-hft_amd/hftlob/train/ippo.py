@@ -34,7 +34,10 @@ initialisation draw from torch's generator, not JAX's threefry, and the network
 runs through torch (rocBLAS GEMMs) rather than XLA.  With ``FUSED_POLICY`` the rollout's
 policy step is one HIP launch per agent type and step (``train.policy.policy_step``) and its
 samples are ``jax.random.categorical`` draws from a carried threefry key, so nothing inside the
-rollout reads torch's generator.  With ``FUSED_LOSS`` the update's GAE is one HIP launch and the
+rollout reads torch's generator.  With ``GROUPED_POLICY`` (on top of ``FUSED_POLICY``) a rollout step's
+policy steps of all the agent types are one launch (``train.policy.policy_step_grouped``), bit for bit the per-type
+launches; ``train.population.PopulationTrainer`` trains several independent runs of one env config in lockstep on it.
+With ``FUSED_LOSS`` the update's GAE is one HIP launch and the
 minibatch step's loss with its gradient three (``train.loss.gae``, ``train.loss.ppo_loss_fused``).
 With ``FUSED_OPT`` the minibatch step's clipping and Adam step are two HIP launches per agent type
 (``train.optim.adam_clip_step``) on capturable Adam's state, so the checkpoints do not change.
@@ -66,7 +69,8 @@ from ..env import MARLEnv, split_keys
 from .gru import MAX_GROUPS, SUPPORTED_HIDDEN, gru_scan, gru_scan_grouped, gru_scan_supported
 from .loss import gae as gae_fused, ppo_loss_fused, ppo_loss_supported
 from .optim import MAX_TENSORS, adam_clip_step, adam_clip_supported, init_adam_state
-from .policy import MAX_ACTIONS, MAX_HEADS, MAX_OBS_DIM, SAMPLE, policy_step_multi_supported, policy_step_net
+from .policy import (MAX_ACTIONS, MAX_GROUPS as MAX_POLICY_GROUPS, MAX_HEADS, MAX_OBS_DIM, SAMPLE, policy_step_grouped,
+                     policy_step_multi_supported, policy_step_net)
 from .wgrad import MAX_P, SUPPORTED_Q, narrow_linear, narrow_linear_supported, wide_linear, wide_linear_supported
 
 
@@ -135,6 +139,8 @@ SWITCHES = [
     Switch("FUSED_GRU", "the PPO update's GRU scan as the fused HIP operators", gpu=False),   # on the CPU: the loop
     Switch("FUSED_POLICY", "the rollout's policy step, sample and log-prob as one fused HIP launch",
            check=_policy_step_check("FUSED_POLICY needs")),
+    Switch("GROUPED_POLICY", "the agent types' policy steps of a rollout step as one fused HIP launch (needs "
+           "--fused-policy)", check=_policy_step_check("GROUPED_POLICY needs")),
     Switch("FUSED_LOSS", "the update's GAE and PPO loss (with its gradient) as fused HIP launches", check=_loss_check),
     Switch("FUSED_OPT", "the minibatch step's global-norm clip and Adam step as two fused HIP launches",
            check=_opt_check),
@@ -359,10 +365,122 @@ def _average_grads(params, dist) -> None:
         o += g.numel()
 
 
+def rollout_members(members: Sequence["IPPOTrainer"], env, state):
+    """NUM_STEPS of _env_step (:578-658) for the trainers ``members`` (one, or the several of a
+    ``PopulationTrainer``) on one env batch whose rows [m E, (m + 1) E) are member m's; returns the env state.
+    Per step: every member's policy side (with GROUPED_POLICY all the members' and types' steps as ONE launch),
+    ONE ``env.step`` whose keys and per-type actions are the members' own concatenated, then every member's
+    rows of the outputs into its buffers.  One member concatenates and slices nothing."""
+    lead, P = members[0], len(members)
+    E = lead.E
+    for t in range(lead.T):
+        jobs: list = []
+        actions = [m._policy_step(t, jobs) for m in members]
+        if jobs:   # GROUPED_POLICY: the arguments of every policy_step_net the members would have launched
+            nets, obss, dones, hs, keys, outs = zip(*jobs)
+            policy_step_grouped(nets, obss, dones, hs, SAMPLE, keys=keys, outs=outs)
+        keys = [m._next_keys() for m in members]
+        if P == 1:
+            keys, acts = keys[0], actions[0]
+        else:
+            keys, acts = torch.cat(keys), [torch.cat(a) for a in zip(*actions)]
+        obs, state, rew, dones, _ = env.step(keys, state, acts, lead.params)
+        for k, m in enumerate(members):
+            if P == 1:
+                m._env_outputs(t, obs, rew, dones)
+                continue
+            r = slice(k * E, (k + 1) * E)
+            m._env_outputs(t, [o[r] for o in obs], [x[r] for x in rew],
+                           {"__all__": dones["__all__"][r], "agents": [d[r] for d in dones["agents"]]})
+    return state
+
+
+def run_rollout(owner, gens, rollout: Callable[[], None]) -> None:
+    """``rollout()`` for ``owner`` (a trainer, or a population of them: its ``graphs``, ``_roll`` and
+    ``_on_side_stream``): eager, or with CUDA_GRAPHS one eager rollout on a side stream (warm-up), then one
+    capture (which runs nothing; ``gens`` are the torch generators it draws from), then replays.  A rollout that
+    cannot be captured stays eager."""
+    if not owner.graphs or owner._roll is False:
+        return rollout()
+    if owner._roll is None:  # one eager rollout (warm-up), then capture; capture runs nothing
+        owner._on_side_stream(rollout)
+        owner._roll = 0
+        return None
+    if owner._roll == 0:
+        g = torch.cuda.CUDAGraph()
+        for gen in gens:
+            g.register_generator_state(gen)
+        try:
+            with torch.cuda.graph(g):
+                rollout()
+        except RuntimeError:  # an op that cannot be captured: stay eager
+            owner._roll = False
+            return rollout()
+        owner._roll = g
+    owner._roll.replay()
+    return None
+
+
+def joint_step(pairs) -> List[torch.Tensor]:
+    """One PPO minibatch step of the (trainer, agent type) ``pairs`` from their static inputs: the forward over
+    the sequences (``forward_grouped``: several nets' scans are grouped), each pair's loss with its trainer's
+    coefficients, one backward, then per pair the grad pmean (multi-rank), the global-norm clip and Adam;
+    returns each pair's loss scalars.  The pairs are one trainer's agent types, or with
+    ``train.population.PopulationTrainer`` those of several trainers with the same switches."""
+    T = pairs[0][0].T
+    nets, bufs, sts = ([getattr(tr, x)[i] for tr, i in pairs] for x in ("nets", "buf", "_st"))
+    idxs = [st["idx"] for st in sts]
+    fw = ActorCriticRNN.forward_grouped(nets, [st["h0"][idx] for st, idx in zip(sts, idxs)],
+                                        [b.obs[:, idx] for b, idx in zip(bufs, idxs)],
+                                        [b.done[:, idx] for b, idx in zip(bufs, idxs)])
+    outs = []
+    for (tr, i), net, b, st, idx, (logits, values) in zip(pairs, nets, bufs, sts, idxs, fw):
+        c = tr.c
+        loss_fn = ppo_loss_fused if tr.fused_loss else ppo_loss_multi
+        outs.append(loss_fn(logits, values, b.action[:, idx].view(T, -1, len(net.heads)), b.value[:, idx],
+                            b.log_prob[:, idx], st["adv"][:, idx], st["tgt"][:, idx], c["CLIP_EPS"], c["VF_COEF"][i],
+                            c["ENT_COEF"][i], net.heads))
+    # the list of totals, not their sum: the grouped scan's backward runs once, when every net's
+    # gradient of its hseq has arrived, and no net's gradient passes through an addition
+    torch.autograd.backward([out[0] for out in outs])
+    for (tr, i), net in zip(pairs, nets):
+        if tr.dist is not None and tr.dist.get_world_size() > 1:
+            _average_grads(list(net.parameters()), tr.dist)
+        if tr.fused_opt:
+            adam_clip_step(tr.opts[i], tr.c["MAX_GRAD_NORM"][i])
+        else:
+            torch.nn.utils.clip_grad_norm_(net.parameters(), tr.c["MAX_GRAD_NORM"][i])
+            tr.opts[i].step()
+    return [torch.stack([x.detach() for x in out]) for out in outs]
+
+
+def run_joint_step(s: Dict, pairs, step: Callable[[], List[torch.Tensor]], graphs: bool, on_side_stream):
+    """``step()``, a ``joint_step`` of ``pairs``, under the record ``s`` (warm, graph, out): eager, or with
+    ``graphs`` two eager steps on a side stream, then one capture (which runs nothing), then replays."""
+    if s["graph"] is None:
+        for tr, i in pairs:
+            tr.opts[i].zero_grad(set_to_none=True)
+        if not graphs:
+            return step()
+        if s["warm"] < 2:
+            r = on_side_stream(step)
+            s["warm"] += 1
+            return r
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            s["out"] = step()
+        s["graph"] = g
+    s["graph"].replay()
+    return [o.clone() for o in s["out"]]
+
+
 class IPPOTrainer:
     """make_train(config)(rng) of the reference, one ``update`` per call."""
 
-    def __init__(self, env: MARLEnv, config: Dict, dist=None, device=None, eval_env: Optional[MARLEnv] = None):
+    def __init__(self, env: MARLEnv, config: Dict, dist=None, device=None, eval_env: Optional[MARLEnv] = None,
+                 reset: bool = True):
+        """reset=False leaves the env alone (``state`` stays None): the caller resets it with ``reset_keys`` and
+        hands the first observations to ``_adopt_obs`` (``train.population``: one env batch for several trainers)."""
         self.env, self.c, self.dist, self.eval_env = env, config, dist, eval_env
         self.device = torch.device(device or env.device)
         nt = len(env.list_of_agents_configs)
@@ -388,6 +506,12 @@ class IPPOTrainer:
             if world > 1:
                 raise ValueError(f"GROUPED_SCAN is single-process (the gradient all-reduce is per agent type), "
                                  f"got a world size of {world}")
+        # GROUPED_POLICY: the agent types' policy steps of a rollout step as one launch (train.policy.policy_step_grouped)
+        if c.get("GROUPED_POLICY", False):
+            if not c.get("FUSED_POLICY", False):
+                raise ValueError("GROUPED_POLICY needs FUSED_POLICY")
+            if nt > MAX_POLICY_GROUPS:
+                raise ValueError(f"GROUPED_POLICY needs <= {MAX_POLICY_GROUPS} agent types, got {nt}")
         self.E, self.T = n_global // world, c["NUM_STEPS"]
         self.n_agents = list(env.multi_agent_config.number_of_agents_per_type)
         self.n_actors = [n * self.E for n in self.n_agents]
@@ -468,8 +592,10 @@ class IPPOTrainer:
             # rng, the reset keys and every env step key are what they are without the switch
             pm = torch.tensor([[0x706F6C, c["SEED"]]], dtype=torch.int32, device=self.device)
             self.pol_rng = self._split(pm, world + 1)[0][rank + 1].clone()
-        obs, self.state = env.reset(reset_keys, self.params)
-        self.last_obs = [o.reshape(n, -1).clone() for o, n in zip(obs, self.n_actors)]
+        self.state = None
+        if reset:
+            obs, self.state = env.reset(reset_keys, self.params)
+            self._adopt_obs(obs)
         self.last_done = [torch.zeros(n, dtype=torch.bool, device=self.device) for n in self.n_actors]
         self.h = [torch.zeros(n, c["GRU_HIDDEN_DIM"], device=self.device) for n in self.n_actors]
         T = self.T
@@ -488,6 +614,10 @@ class IPPOTrainer:
                      "idx": torch.zeros(n // c["NUM_MINIBATCHES"], dtype=torch.long, device=self.device)}
                     for n in self.n_actors]
 
+    def _adopt_obs(self, obs) -> None:
+        """The first observations after the reset, per agent type [E, n, D]."""
+        self.last_obs = [o.reshape(n, -1).clone() for o, n in zip(obs, self.n_actors)]
+
     def _next_keys(self) -> torch.Tensor:
         """rng, _rng = split(rng); rng_step = split(_rng, NUM_ENVS) (:613-614)."""
         k = self._split(self.rng[None], 2)[0]
@@ -498,24 +628,7 @@ class IPPOTrainer:
     def rollout(self) -> None:
         """NUM_STEPS of _env_step (:578-658), all on the device; with CUDA_GRAPHS the whole
         rollout (policy, sampling, env steps, buffer writes) is one captured HIP graph."""
-        if not self.graphs or self._roll is False:
-            return self._rollout()
-        if self._roll is None:  # one eager rollout (warm-up), then capture; capture runs nothing
-            self._on_side_stream(self._rollout)
-            self._roll = 0
-            return None
-        if self._roll == 0:
-            g = torch.cuda.CUDAGraph()
-            g.register_generator_state(self.gen)
-            try:
-                with torch.cuda.graph(g):
-                    self._rollout()
-            except RuntimeError:  # an op that cannot be captured: stay eager
-                self._roll = False
-                return self._rollout()
-            self._roll = g
-        self._roll.replay()
-        return None
+        return run_rollout(self, [self.gen], self._rollout)
 
     def _on_side_stream(self, fn):
         """fn() on a side stream between two joins with the current one: how eager work runs ahead of a capture."""
@@ -527,87 +640,61 @@ class IPPOTrainer:
         return r
 
     def _rollout(self) -> None:
-        for t in range(self.T):
-            actions = []
-            for i, net in enumerate(self.nets):
-                b = self.buf[i]
-                b.obs[t].copy_(self.last_obs[i])
-                b.done[t].copy_(self.last_done[i])
-                # the env's view of the step's action words: [E, n] for a Discrete type, [E, n, K] otherwise
-                actions.append(b.action[t].view(net.action_shape(self.E, self.n_agents[i])))
-                if self.fused_policy:  # pol_rng, sub = split(pol_rng); one launch: carry in place, outputs into the buffers
-                    k = self._split(self.pol_rng[None], 2)[0]
-                    self.pol_rng.copy_(k[0])
-                    policy_step_net(net, self.last_obs[i], self.last_done[i], self.h[i], SAMPLE, key=k[1],
-                                    out=(b.action[t], b.log_prob[t], b.value[t]))
-                    continue
-                h, logits, v = net.step(self.h[i], self.last_obs[i], self.last_done[i])
-                self.h[i].copy_(h)
-                b.value[t].copy_(v)
-                # one draw per head, in head order; log_prob adds the heads' from the first one's
-                words = b.action[t].view(self.n_actors[i], len(net.heads))
-                for k, lg in enumerate(logits.split(net.heads, -1)):
-                    a = torch.multinomial(torch.softmax(lg, -1), 1, generator=self.gen)
-                    words[:, k].copy_(a.squeeze(-1))
-                    lpk = torch.log_softmax(lg, -1).gather(-1, a).squeeze(-1)
-                    lp = lpk if k == 0 else lp + lpk
-                b.log_prob[t].copy_(lp)
-            obs, self.state, rew, dones, _ = self.env.step(self._next_keys(), self.state, actions, self.params)
-            for i in range(self.n_types):
-                b = self.buf[i]
-                b.reward[t].copy_(rew[i].reshape(-1))
-                b.global_done[t].copy_(dones["__all__"].repeat_interleave(self.n_agents[i]))
-                self.last_obs[i].copy_(obs[i].reshape(self.n_actors[i], -1))
-                self.last_done[i].copy_(dones["agents"][i].reshape(-1))
+        self.state = rollout_members([self], self.env, self.state)
+
+    def _policy_step(self, t: int, jobs: list) -> list:
+        """The policy side of rollout step t: per agent type the obs and done rows into the buffers, then the
+        type's step, sample and log-prob.  Returns the env's view of the step's action words per type.  With
+        GROUPED_POLICY the types' steps are not launched here but appended to ``jobs`` as the arguments of
+        ``policy_step_net``, for the caller's one grouped launch; ``pol_rng`` is split per type in type order
+        either way."""
+        actions = []
+        for i, net in enumerate(self.nets):
+            b = self.buf[i]
+            b.obs[t].copy_(self.last_obs[i])
+            b.done[t].copy_(self.last_done[i])
+            # the env's view of the step's action words: [E, n] for a Discrete type, [E, n, K] otherwise
+            actions.append(b.action[t].view(net.action_shape(self.E, self.n_agents[i])))
+            if self.fused_policy:  # pol_rng, sub = split(pol_rng); one launch: carry in place, outputs into the buffers
+                k = self._split(self.pol_rng[None], 2)[0]
+                self.pol_rng.copy_(k[0])
+                job = (net, self.last_obs[i], self.last_done[i], self.h[i], k[1], (b.action[t], b.log_prob[t], b.value[t]))
+                if self.grouped_policy:
+                    jobs.append(job)
+                else:
+                    policy_step_net(*job[:4], SAMPLE, key=job[4], out=job[5])
+                continue
+            h, logits, v = net.step(self.h[i], self.last_obs[i], self.last_done[i])
+            self.h[i].copy_(h)
+            b.value[t].copy_(v)
+            # one draw per head, in head order; log_prob adds the heads' from the first one's
+            words = b.action[t].view(self.n_actors[i], len(net.heads))
+            for k, lg in enumerate(logits.split(net.heads, -1)):
+                a = torch.multinomial(torch.softmax(lg, -1), 1, generator=self.gen)
+                words[:, k].copy_(a.squeeze(-1))
+                lpk = torch.log_softmax(lg, -1).gather(-1, a).squeeze(-1)
+                lp = lpk if k == 0 else lp + lpk
+            b.log_prob[t].copy_(lp)
+        return actions
+
+    def _env_outputs(self, t: int, obs, rew, dones) -> None:
+        """The env side of rollout step t: this trainer's rows of the step's outputs into its buffers."""
+        for i in range(self.n_types):
+            b = self.buf[i]
+            b.reward[t].copy_(rew[i].reshape(-1))
+            b.global_done[t].copy_(dones["__all__"].repeat_interleave(self.n_agents[i]))
+            self.last_obs[i].copy_(obs[i].reshape(self.n_actors[i], -1))
+            self.last_done[i].copy_(dones["agents"][i].reshape(-1))
 
     def _step(self, types: List[int]) -> List[torch.Tensor]:
-        """One PPO minibatch step of the agent types ``types`` from their static inputs: the forward over the
-        sequences (``forward_grouped``: several types' scans are grouped), each type's loss, one backward, then
-        per type the grad pmean (multi-rank), the global-norm clip and Adam; returns each type's loss scalars."""
-        c, T = self.c, self.T
-        nets, bufs, sts = ([x[i] for i in types] for x in (self.nets, self.buf, self._st))
-        idxs = [st["idx"] for st in sts]
-        fw = ActorCriticRNN.forward_grouped(nets, [st["h0"][idx] for st, idx in zip(sts, idxs)],
-                                            [b.obs[:, idx] for b, idx in zip(bufs, idxs)],
-                                            [b.done[:, idx] for b, idx in zip(bufs, idxs)])
-        loss_fn = ppo_loss_fused if self.fused_loss else ppo_loss_multi
-        outs = []
-        for i, net, b, st, idx, (logits, values) in zip(types, nets, bufs, sts, idxs, fw):
-            outs.append(loss_fn(logits, values, b.action[:, idx].view(T, -1, len(net.heads)), b.value[:, idx],
-                                b.log_prob[:, idx], st["adv"][:, idx], st["tgt"][:, idx], c["CLIP_EPS"], c["VF_COEF"][i],
-                                c["ENT_COEF"][i], net.heads))
-        # the list of totals, not their sum: the grouped scan's backward runs once, when every type's
-        # gradient of its hseq has arrived, and no type's gradient passes through an addition
-        torch.autograd.backward([out[0] for out in outs])
-        for i, net in zip(types, nets):
-            if self.dist is not None and self.dist.get_world_size() > 1:
-                _average_grads(list(net.parameters()), self.dist)
-            if self.fused_opt:
-                adam_clip_step(self.opts[i], c["MAX_GRAD_NORM"][i])
-            else:
-                torch.nn.utils.clip_grad_norm_(net.parameters(), c["MAX_GRAD_NORM"][i])
-                self.opts[i].step()
-        return [torch.stack([x.detach() for x in out]) for out in outs]
+        """One PPO minibatch step of the agent types ``types`` (``joint_step`` of this trainer's pairs)."""
+        return joint_step([(self, i) for i in types])
 
     def _run_step(self, s: Dict) -> List[torch.Tensor]:
-        """``_step`` of the step group with record ``s``: eager, or with CUDA_GRAPHS two eager steps on a side
-        stream, then one capture (which runs nothing), then replays."""
+        """``_step`` of the step group with record ``s``, eager or captured (``run_joint_step``)."""
         types = s["types"]
-        if s["graph"] is None:
-            for i in types:
-                self.opts[i].zero_grad(set_to_none=True)
-            if not self.graphs:
-                return self._step(types)
-            if s["warm"] < 2:
-                r = self._on_side_stream(lambda: self._step(types))
-                s["warm"] += 1
-                return r
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                s["out"] = self._step(types)
-            s["graph"] = g
-        s["graph"].replay()
-        return [o.clone() for o in s["out"]]
+        return run_joint_step(s, [(self, i) for i in types], lambda: self._step(types), self.graphs,
+                              self._on_side_stream)
 
     def _prepare(self, i: int, h0: torch.Tensor) -> None:
         """After the rollout: agent type i's last value, GAE and the static inputs of its minibatch steps."""
@@ -638,10 +725,7 @@ class IPPOTrainer:
         self.rollout()
         for i in range(self.n_types):
             self._prepare(i, h0[i])
-        # every permutation up front, type 0's epochs, then type 1's, ...: the generator goes through one
-        # sequence whatever the step groups are
-        perms = [[torch.randperm(n, device=self.device, generator=self.gen).view(mb, n // mb)
-                  for _ in range(c["UPDATE_EPOCHS"])] for n in self.n_actors]
+        perms = self._perms()
         stats = [torch.zeros(6, device=self.device) for _ in range(self.n_types)]
         for s in self._steps:
             for e in range(c["UPDATE_EPOCHS"]):
@@ -652,6 +736,19 @@ class IPPOTrainer:
                     for i, r in zip(s["types"], self._run_step(s)):
                         stats[i] += r
                         self.opt_count[i] += 1
+        return self._metrics(stats)
+
+    def _perms(self) -> List[List[torch.Tensor]]:
+        """An update's permutations of the actors, [type][epoch] as [NUM_MINIBATCHES, n // NUM_MINIBATCHES]."""
+        # every permutation up front, type 0's epochs, then type 1's, ...: the generator goes through one
+        # sequence whatever the step groups are
+        c, mb = self.c, self.c["NUM_MINIBATCHES"]
+        return [[torch.randperm(n, device=self.device, generator=self.gen).view(mb, n // mb)
+                 for _ in range(c["UPDATE_EPOCHS"])] for n in self.n_actors]
+
+    def _metrics(self, stats: List[torch.Tensor]) -> Dict:
+        """An update's metrics from each type's summed loss scalars; the update is counted."""
+        c, mb = self.c, self.c["NUM_MINIBATCHES"]
         metrics = {"loss": [], "avg_reward": []}
         for i, b in enumerate(self.buf):
             stats[i] /= c["UPDATE_EPOCHS"] * mb
@@ -773,7 +870,8 @@ def train(env: MARLEnv, config: Dict, n_updates: Optional[int] = None, dist=None
 
 def main(argv=None) -> None:
     """python -m hftlob.train.ippo [--rl-config ippo.yaml] [--env-config 2_player_fq_fqc] [--updates N]
-    [switch flags: one per row of SWITCHES, --fused-gru ... --calc-eval]"""
+    [switch flags: one per row of SWITCHES, --fused-gru ... --calc-eval]
+    [--seeds 2,3,4,5 [--overrides sweep.yaml]]: the runs of a sweep as one population (train.population)"""
     import argparse
     import json
     import yaml
@@ -786,6 +884,10 @@ def main(argv=None) -> None:
     for sw in SWITCHES:
         ap.add_argument(sw.flag, action="store_true", help=sw.help)
     ap.add_argument("--save", default=None, metavar="PATH", help="write a checkpoint here after the last update")
+    ap.add_argument("--seeds", default=None, metavar="S0,S1,...", help="train one independent run per seed in lockstep "
+                    "in this process (train.population.PopulationTrainer); --save PATH writes PATH.m0, PATH.m1, ...")
+    ap.add_argument("--overrides", default=None, metavar="YAML", help="with --seeds: a YAML list of per-member dicts "
+                    "over LR, GAMMA, GAE_LAMBDA, CLIP_EPS, ENT_COEF, VF_COEF, MAX_GRAD_NORM, ANNEAL_LR, TOTAL_TIMESTEPS, SEED")
     ap.add_argument("--data", default=None, help="'lobster' to load world_config.dataPath (else synthetic)")
     a = ap.parse_args(argv)
     c = default_config()
@@ -802,6 +904,19 @@ def main(argv=None) -> None:
     env = MARLEnv(None, cfg, data=a.data, return_info=False, persistent_outputs=True)
     if not a.env_config.endswith((".json", ".yaml")):
         env.config_name = a.env_config   # what a checkpoint records instead of the config's dict
+    if a.overrides and not a.seeds:
+        raise ValueError("--overrides needs --seeds")
+    if a.seeds:
+        from . import population as P
+        seeds = P.parse_seeds(a.seeds)
+        configs = P.member_configs(c, seeds, P.load_overrides(a.overrides, len(seeds)) if a.overrides else None)
+        pop, sps = P.train_population(env, configs, a.updates, log=lambda m: print(json.dumps(m)))
+        if a.save:
+            for k, m in enumerate(pop.members):
+                m.save_checkpoint(f"{a.save}.m{k}")
+        print(json.dumps({"env_steps_per_s_incl_learner": sps, "members": len(seeds), "num_envs": c["NUM_ENVS"],
+                          "num_steps": c["NUM_STEPS"]}))
+        return
     eval_env = None
     if c["CALC_EVAL"]:
         from ..data.synthetic import generate_day

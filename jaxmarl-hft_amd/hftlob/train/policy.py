@@ -13,7 +13,9 @@ action space (``hftlob_policy_step_multi``): K categorical heads on the shared a
 head after head; head k samples with ``jax.random.split(key, K)[k]``, and one head is the
 single-head operator with the key unsplit, as the reference collapses a list of one.  Both pairs
 are one body over a list of head widths; ``policy_step_net`` steps an ``ActorCriticRNN`` through
-the operator its heads need.
+the operator its heads need.  ``policy_step_grouped`` steps up to 8 independent nets, each as
+``policy_step_net`` would, in one launch (``hftlob_policy_step_grouped``); its spec,
+``policy_step_grouped_reference``, is the per-net reference in a loop.
 
 Sampling (mode 0) is ``jax.random.categorical(key, logits)``: the first argmax of
 ``logits + g`` with ``g = jax.random.gumbel(key, (B, A))`` under the partitionable threefry
@@ -205,10 +207,12 @@ def _weights_struct(W: Dict[str, torch.Tensor], D: int, FC: int, H: int, A: int)
     return s
 
 
-def _fused_call(op: str, net, obs, done, h, mode: int, heads, flat: bool, key, out, h_out, logits: bool):
-    """The two operators' shared host side: shape checks, output allocation, the heads' keys and the
-    one launch, for the heads' widths ``heads`` over the rows of ``actor2``.  flat: the one head of
-    hftlob_policy_step, whose action is [B]; else hftlob_policy_step_multi's [B, K]."""
+def _call_args(op: str, net, obs, done, h, mode: int, heads, flat: bool, key, out, h_out, logits: bool):
+    """The operators' shared host side for one batch: shape checks, output allocation and the heads' keys,
+    for the heads' widths ``heads`` over the rows of ``actor2``.  flat: the one head of hftlob_policy_step,
+    whose action is [B]; else hftlob_policy_step_multi's [B, K].  Returns the sizes (B, D, FC, H, K, A),
+    the weight struct and the tensors of the launch (obs, done, h, h_out, key or None, action, log_prob,
+    value, logits or None)."""
     W = net_weights(net)
     if obs.dim() != 2 or h.dim() != 2:
         raise ValueError(f"{op}: obs must be [B, D] and h [B, H]")
@@ -238,17 +242,24 @@ def _fused_call(op: str, net, obs, done, h, mode: int, heads, flat: bool, key, o
         if tuple(t.shape) != shape or t.dtype != dt or t.device != dev:
             raise ValueError(f"{op}: {name} must be {dt} {list(shape)} on {dev}, got {t.dtype} "
                              f"{list(t.shape)} on {t.device}")
-    kp = None
     if mode == SAMPLE:
         if key is None or key.dtype not in (torch.int32, torch.uint32) or key.numel() != 2 or key.device != dev:
             raise ValueError(f"{op}: mode 0 needs key, a uint32/int32 tensor of 2 words on {dev}")
         if K > 1:   # head_keys on the device: [K, 2], one more small launch (one head takes the key unsplit)
             from ..env import split_keys
             key = split_keys(key.reshape(1, 2), K)[0]
-        kp = _lib.ptr(key)
-    ws = _weights_struct(W, D, FC, H, A)
-    args = (C.byref(ws), _lib.ptr(obs), _lib.ptr(done), _lib.ptr(h), _lib.ptr(h_out), int(mode), kp, _lib.ptr(action),
-            _lib.ptr(log_prob), _lib.ptr(value), _lib.ptr(lg), _lib.stream_ptr(device=dev))
+    else:
+        key = None
+    return (B, D, FC, H, K, A), _weights_struct(W, D, FC, H, A), (obs, done, h, h_out, key, action, log_prob, value, lg)
+
+
+def _fused_call(op: str, net, obs, done, h, mode: int, heads, flat: bool, key, out, h_out, logits: bool):
+    """One batch through its operator: ``_call_args`` and the one launch."""
+    (B, D, FC, H, K, A), ws, ts = _call_args(op, net, obs, done, h, mode, heads, flat, key, out, h_out, logits)
+    obs, done, h, h_out, key, action, log_prob, value, lg = ts
+    dev = obs.device
+    args = (C.byref(ws), _lib.ptr(obs), _lib.ptr(done), _lib.ptr(h), _lib.ptr(h_out), int(mode), _lib.ptr(key),
+            _lib.ptr(action), _lib.ptr(log_prob), _lib.ptr(value), _lib.ptr(lg), _lib.stream_ptr(device=dev))
     with torch.cuda.device(dev):
         if flat:
             rc = _lib.lib().hftlob_policy_step(B, D, FC, H, A, *args)
@@ -290,3 +301,90 @@ def policy_step_net(net, obs, done, h, mode: int, key=None, out=None):
     flat = net.action_shape() == ()
     return _fused_call("policy_step" if flat else "policy_step_multi", net, obs, done, h, mode, net.heads, flat, key,
                        out, None, False)
+
+
+# ------------------------------------------------------------------ several nets in one launch
+MAX_GROUPS = 8   # HFTLOB_POLICY_MAX_GROUPS: the nets of one hftlob_policy_step_grouped launch
+
+
+def _net_heads(net, heads):
+    """(the heads' widths, flat) of a group: ``heads`` as given (an int is the one flat head of
+    hftlob_policy_step, a list the heads of hftlob_policy_step_multi), else what ``policy_step_net`` takes
+    from the net."""
+    if heads is None:
+        if isinstance(net, dict):
+            raise ValueError("a dict of weights carries no action space: give its heads")
+        return list(net.heads), net.action_shape() == ()
+    if isinstance(heads, int):
+        return [heads], True
+    return [int(n) for n in heads], False
+
+
+def policy_step_grouped_supported(nets, heads=None) -> bool:
+    """Whether one grouped launch can step these nets (no GPU needed to ask): 1..8 of them, one
+    FC_DIM_SIZE and one GRU_HIDDEN_DIM among them, and each one within the single operators' sizes."""
+    nets = list(nets)
+    if not 1 <= len(nets) <= MAX_GROUPS:
+        return False
+    Ws = [net_weights(n) for n in nets]
+    FC, H = Ws[0]["w_embed"].shape[0], Ws[0]["w_hh"].shape[1]
+    heads = [None] * len(nets) if heads is None else list(heads)
+    return all(W["w_embed"].shape[0] == FC and W["w_hh"].shape[1] == H
+               and policy_step_multi_supported(W["w_embed"].shape[1], FC, H, _net_heads(n, hd)[0])
+               and sum(_net_heads(n, hd)[0]) == W["w_a2"].shape[0] for n, W, hd in zip(nets, Ws, heads))
+
+
+def policy_step_grouped_reference(nets, obss, dones, hs, mode: int, keys=None, heads=None):
+    """hftlob_policy_step_grouped in torch: the per-group reference in a loop.  A list of
+    (h, logits, value, action, log_prob) as ``policy_step_multi_reference`` returns them, the action of a
+    flat one-head group [B] as ``policy_step_reference``'s."""
+    out = []
+    for g, (net, obs, done, h) in enumerate(zip(nets, obss, dones, hs)):
+        hd, flat = _net_heads(net, None if heads is None else heads[g])
+        r = policy_step_multi_reference(net, obs, done, h, mode, hd, key=None if keys is None else keys[g])
+        out.append(r[:3] + (r[3].squeeze(-1),) + r[4:] if flat else r)
+    return out
+
+
+def policy_step_grouped(nets, obss, dones, hs, mode: int, keys=None, outs=None, heads=None, h_outs=None,
+                        logits: bool = False):
+    """hftlob_policy_step_grouped on device tensors: one launch on torch's current stream that steps
+    every net of ``nets`` (at most 8, of one FC_DIM_SIZE and GRU_HIDDEN_DIM) on its own batch.  Group g
+    is what ``policy_step_net(nets[g], obss[g], dones[g], hs[g], mode, keys[g], outs[g])`` is, bit for
+    bit: the same operator for the net's action space, the same split of the key into the heads' keys
+    (one small launch per multi-head group in mode 0; nothing synchronises), the carry updated in place.
+    ``heads`` (per group an int, a list, or None for the net's own), ``h_outs`` and ``logits`` are what
+    ``policy_step`` / ``policy_step_multi`` take.  Returns a list of
+    ``(h_out, action, log_prob, value, logits or None)``."""
+    nets = list(nets)
+    G = len(nets)
+    op = "policy_step_grouped"
+    if not 1 <= G <= MAX_GROUPS:
+        raise ValueError(f"{op} takes 1..{MAX_GROUPS} nets, got {G}")
+    if not len(obss) == len(dones) == len(hs) == G:
+        raise ValueError(f"{op}: obss, dones and hs must have one entry per net")
+    opt = lambda xs: [None] * G if xs is None else list(xs)  # noqa: E731
+    keys, outs, heads, h_outs = opt(keys), opt(outs), opt(heads), opt(h_outs)
+    groups = (_lib.PolicyGroup * G)()
+    keep, res = [], []
+    FC = H = dev = None
+    for g, net in enumerate(nets):
+        hd, flat = _net_heads(net, heads[g])
+        (B, D, fc, hh, K, A), ws, ts = _call_args(f"{op}: group {g}", net, obss[g], dones[g], hs[g], mode, hd, flat,
+                                                  keys[g], outs[g], h_outs[g], logits)
+        if g == 0:
+            FC, H, dev = fc, hh, ts[0].device
+        elif (fc, hh) != (FC, H) or ts[0].device != dev:
+            raise ValueError(f"{op}: the groups share FC_DIM_SIZE, GRU_HIDDEN_DIM and the device; group 0 has "
+                             f"{FC}, {H} on {dev}, group {g} {fc}, {hh} on {ts[0].device}")
+        x = groups[g]
+        x.B, x.D, x.K, x.w = B, D, K, ws
+        for k, n in enumerate(hd):
+            x.nvec[k] = n
+        for name, t in zip(("obs", "done", "h_in", "h_out", "keys", "action", "log_prob", "value", "logits"), ts):
+            setattr(x, name, _lib.ptr(t))
+        keep.append(ts)   # (the split keys live until the launch is queued)
+        res.append((ts[3], ts[5], ts[6], ts[7], ts[8]))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().hftlob_policy_step_grouped(FC, H, G, groups, int(mode), _lib.stream_ptr(device=dev)))
+    return res

@@ -6,10 +6,7 @@ REV=${1:-HEAD}
 NAME=${2:-prev}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d /tmp/hftlob_rev.XXXX)
-mkdir -p $T/jaxmarl-hft_amd/csrc $T/include
-git -C $ROOT show $REV:jaxmarl-hft_amd/csrc/hftlob.hip > $T/jaxmarl-hft_amd/csrc/hftlob.hip
-git -C $ROOT show $REV:jaxmarl-hft_amd/csrc/Makefile > $T/jaxmarl-hft_amd/csrc/Makefile
-git -C $ROOT show $REV:include/hftlob.h > $T/include/hftlob.h
+git -C $ROOT archive $REV jaxmarl-hft_amd/csrc include | tar -x -C $T   # every source file of the revision
 mkdir -p $ROOT/ab
 make -C $T/jaxmarl-hft_amd/csrc -j8 OUT=$ROOT/ab/lib_$NAME.so > $T/build.log 2>&1 || { tail -20 $T/build.log; exit 1; }
 rm -rf $T

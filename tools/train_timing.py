@@ -1,9 +1,13 @@
 """Time the IPPO learner's phases on the GPU (rollout vs PPO epochs) at the metric config.
 
-    python tools/train_timing.py [--graph] [--updates N] [switch flags]
+    python tools/train_timing.py [--graph] [--updates N] [--envs E] [--seed S] [--population P] [switch flags]
 
 --graph: CUDA_GRAPHS (the rollout and each minibatch step replayed as HIP graphs);
 --updates N: the timed rollout + update rounds after the first, untimed update (default 3);
+--envs E: NUM_ENVS (default 4096);
+--seed S: SEED (default 2);
+--population P: P independent runs (seeds S, S + 1, ...) of E envs each as one hftlob.train.population.PopulationTrainer
+instead of one IPPOTrainer; the env-steps/s are those of all the members;
 the switch flags are the learner's own (hftlob.train.ippo.SWITCHES, but for CALC_EVAL: the evaluation is no part of
 the update that is timed):
 """
@@ -21,6 +25,7 @@ from hftlob.config_io import builtin_config  # noqa: E402
 from hftlob.data.synthetic import generate_day  # noqa: E402
 from hftlob.env import MARLEnv  # noqa: E402
 from hftlob.train import ippo as I  # noqa: E402
+from hftlob.train.population import PopulationTrainer  # noqa: E402
 
 TIMED = [sw for sw in I.SWITCHES if sw.key != "CALC_EVAL"]
 __doc__ += "".join(f"{sw.flag}: {sw.key} ({sw.help});\n" for sw in TIMED)
@@ -30,6 +35,9 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--updates", type=int, default=3)
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--population", type=int, default=0)
+    ap.add_argument("--seed", type=int, default=2, help="SEED of the run (a population's members: seed, seed + 1, ...)")
     for sw in TIMED:
         ap.add_argument(sw.flag, action="store_true")
     a = ap.parse_args()
@@ -37,9 +45,13 @@ def main():
     w = cfg.world_config
     day = generate_day(n_msgs=100_000, seed=4, snap_every=w.n_data_msg_per_step * w.start_resolution)
     env = MARLEnv(None, cfg, data=day, return_info=False, persistent_outputs=True)
-    c = I.default_config(NUM_ENVS=4096, NUM_STEPS=64, TOTAL_TIMESTEPS=4096 * 64 * 50, CUDA_GRAPHS=a.graph,
+    c = I.default_config(NUM_ENVS=a.envs, NUM_STEPS=64, TOTAL_TIMESTEPS=a.envs * 64 * 50, CUDA_GRAPHS=a.graph, SEED=a.seed,
                          **{sw.key: getattr(a, sw.key.lower()) for sw in TIMED})
-    tr = I.IPPOTrainer(env, c)
+    if a.population:
+        tr = PopulationTrainer(env, [dict(c, SEED=a.seed + m) for m in range(a.population)])
+    else:
+        tr = I.IPPOTrainer(env, c)
+    steps = a.envs * 64 * max(a.population, 1)
     tr.update()
     torch.cuda.synchronize()
     for _ in range(a.updates):
@@ -51,7 +63,7 @@ def main():
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         print(f"rollout {1e3 * (t1 - t0):.1f} ms  full update (rollout + epochs) {1e3 * (t2 - t1):.1f} ms  "
-              f"-> {4096 * 64 / (t2 - t1):.0f} env-steps/s", flush=True)
+              f"-> {steps / (t2 - t1):.0f} env-steps/s", flush=True)
 
 
 if __name__ == "__main__":
