@@ -30,6 +30,10 @@
  *   hftlob_draw_actions / hftlob_env_rollout_eval_drawn <- the same scripts' multi-action FixedAction
  *                           (baseline_only_JAXMARL.py:58-71) and baseline_JAXMARL.py:367-374
  *                           RandomPolicy: an action drawn uniformly from a set at every step.
+ *   hftlob_env_rollout_eval_episodes / hftlob_env_rollout_eval_drawn_episodes / hftlob_eval_tally_episodes
+ *                        <- the per-episode reward arrays [episodes, agents] those evaluations feed to
+ *                           baseline_eval/plotting_combinations.py (load_data), and the episodes' lengths
+ *                           and end-of-episode info words beside them.
  *   hftlob_sample_actions<- jaxen/Speed_test.py:166-177 (per-env random actions
  *                           via gymnax Discrete.sample = jax.random.randint).
  *   hftlob_split_keys    <- jax.random.split(key, n) (threefry2x32), batched.
@@ -421,6 +425,33 @@ int hftlob_env_rollout_eval(const hftlob_env_cfg* cfg /*[host]*/, int n_env, int
                             const int32_t* init_states, int32_t* state, double* stats,
                             const hftlob_step_out* out /*[host] struct*/, void* stream);
 
+/* Per-episode records — the arrays the reference's evaluation plots read
+ * (baseline_eval/plotting_combinations.py: episode rewards [episodes, agents] per combination), which
+ * the sums above cannot give back.  One record of HFTLOB_EPISODE_WORDS doubles per (env, agent,
+ * completed episode), holding exactly the values the accumulators add at the episode's last step:
+ *   0              the episode's reward sum (the double added to stats word 4)
+ *   1              the episode's length (the double added to word 6)
+ *   2+k            (k = 0..23) info word k at the episode's last step, widened as for words 58+2k
+ * episodes double [n_env][n_agents][ep_cap][HFTLOB_EPISODE_WORDS].  The record of a step whose done_all
+ * is set goes to index i = the agent's stats word 1 before that step's increment: the episodes
+ * completed so far, what a given `stats` carried in included.  It is written iff 0 <= i < ep_cap; a slot
+ * the call does not write is left untouched.  The index is word 1, so a run cut into calls carries
+ * nothing beyond its `stats` and the same `episodes`, and overflow shows as word 1 > ep_cap.  No
+ * counter of its own, no atomics: every record is the same bits on every call, and bit for bit what
+ * hftlob/evaluate.py reduce_steps(max_episodes=) gives.
+ * hftlob_env_rollout_eval_episodes is hftlob_env_rollout_eval with such a buffer: the same kernels (the
+ * entry point without a buffer passes them none), the same state, `out` and `stats` bit for bit.  The
+ * lanes of the env's wave that hold the values at the tally store them (26 stores per agent and
+ * episode end).  HFTLOB_EINVAL: episodes NULL or ep_cap < 1; everything else is refused as
+ * hftlob_env_rollout_eval refuses it. */
+#define HFTLOB_EPISODE_WORDS 26
+int hftlob_env_rollout_eval_episodes(const hftlob_env_cfg* cfg /*[host]*/, int n_env, int n_steps, const uint32_t* keys,
+                                     const int32_t* actions, int actions_fixed, const int32_t* msg_data,
+                                     const int32_t* init_states, int32_t* state, double* stats,
+                                     const hftlob_step_out* out /*[host] struct*/,
+                                     double* episodes /*[n_env][n_agents][ep_cap][HFTLOB_EPISODE_WORDS]*/, int ep_cap,
+                                     void* stream);
+
 /* The accumulators above from per-step outputs, as one launch — replaces the reduction of the
  * trajectory batch in baseline_eval/baseline_JAXMARL.py (:819-951) for a caller whose actions do not
  * come from the env launch (a policy network: hftlob/evaluate.py evaluate_policy), and who therefore
@@ -446,6 +477,20 @@ int hftlob_eval_tally(int n_env, int n_agents, int n_steps, int info_words,
                       const uint8_t* done_all /*[n_steps][n_env]*/,
                       const uint32_t* float_words /*[n_agents], host*/,
                       double* stats /*[n_env][n_agents][HFTLOB_EVAL_WORDS], in/out*/, void* stream);
+
+/* hftlob_eval_tally with the per-episode records of hftlob_env_rollout_eval_episodes (the same buffer,
+ * the same index rule, the same bits): at a step with done_all set the lane of quantity q stores its
+ * own word of the record (q = 0: words 0 and 1; q >= 1: word 1 + q).  Every lane counts the agent's
+ * episodes itself from stats word 1, so no lane talks to another.  HFTLOB_EINVAL: episodes NULL or
+ * ep_cap < 1; everything else is refused as hftlob_eval_tally refuses it. */
+int hftlob_eval_tally_episodes(int n_env, int n_agents, int n_steps, int info_words,
+                               const float* rewards /*[n_steps][n_env][n_agents]*/,
+                               const int32_t* info /*[n_steps][n_env][info_words]*/,
+                               const uint8_t* done_all /*[n_steps][n_env]*/,
+                               const uint32_t* float_words /*[n_agents], host*/,
+                               double* stats /*[n_env][n_agents][HFTLOB_EVAL_WORDS], in/out*/,
+                               double* episodes /*[n_env][n_agents][ep_cap][HFTLOB_EPISODE_WORDS]*/, int ep_cap,
+                               void* stream);
 
 /* The drawn actions of a uniform baseline policy for a batch of actors, as one launch — replaces the
  * per-step pi.sample of the reference's multi-action FixedAction (baseline_eval/
@@ -488,6 +533,18 @@ int hftlob_env_rollout_eval_drawn(const hftlob_env_cfg* cfg /*[host]*/, int n_en
                                   int32_t* actions_out /*[n_steps][n_env][action_words] or NULL*/,
                                   const int32_t* msg_data, const int32_t* init_states, int32_t* state, double* stats,
                                   const hftlob_step_out* out /*[host] struct*/, void* stream);
+
+/* hftlob_env_rollout_eval_drawn with the per-episode records of hftlob_env_rollout_eval_episodes (the
+ * same buffer, index rule and bits).  HFTLOB_EINVAL: episodes NULL or ep_cap < 1; everything else is
+ * refused as hftlob_env_rollout_eval_drawn refuses it. */
+int hftlob_env_rollout_eval_drawn_episodes(const hftlob_env_cfg* cfg /*[host]*/, int n_env, int n_steps,
+                                           const uint32_t* keys, const uint32_t* draw_keys /*[n_steps][n_types][2]*/,
+                                           const uint32_t* allowed /*[n_types], host*/,
+                                           int32_t* actions_out /*[n_steps][n_env][action_words] or NULL*/,
+                                           const int32_t* msg_data, const int32_t* init_states, int32_t* state,
+                                           double* stats, const hftlob_step_out* out /*[host] struct*/,
+                                           double* episodes /*[n_env][n_agents][ep_cap][HFTLOB_EPISODE_WORDS]*/,
+                                           int ep_cap, void* stream);
 
 /* Creates the library streams / events hftlob_env_rollout_sampled needs for n_slices
  * slices on the device of `stream` (host-only; idempotent). */

@@ -3392,6 +3392,17 @@ __global__ __launch_bounds__(64) void k_book_process_depth(hftlob_lob_cfg cfg, i
 // after it, so their latency (HBM, or L2 after the launch's first step) lies under the reward's.
 // The float words of the agents' info blocks (hftlob/layout.py INFO_MM / INFO_EXE), as bit masks:
 constexpr u32 INFO_F32_MM = 0xC0B9FFu, INFO_F32_EXE = 0x13Cu;
+// The per-episode records' buffer of the evaluation kernels (rows: double [n_env][n_agents][cap]
+// [HFTLOB_EPISODE_WORDS], nullptr for none): their third argument, by value, after the config and n_env
+// in the kernarg segment.  The step reads it there (kep_t, scalar loads) inside the tally's episode-end
+// branch only, so neither word is carried in registers through the step.
+struct EpisodeBuf {
+    double* rows;
+    int cap;
+};
+typedef const __attribute__((address_space(4))) EpisodeBuf kep_t;
+constexpr size_t EPISODE_BUF_KERNARG =
+    (sizeof(hftlob_env_cfg) + sizeof(int) + alignof(EpisodeBuf) - 1) / alignof(EpisodeBuf) * alignof(EpisodeBuf);
 constexpr u32 TALLY_SUM_LANES = 0x34u;  // header lanes (bit lane - 32) whose second word is the running sum
 struct TallyLane { double a, b; };
 DEV int tally_word(int l) { return l < 25 ? 8 + 2 * l : (l < 40 ? l - 32 : 58 + 2 * (l - 40)); }
@@ -3409,8 +3420,14 @@ DEV TallyLane tally_load(const double* row, bool all) {
 // rew / iw: the agent's reward as stored to `rewards` and its info words (wave-uniform); f32: the
 // kind's float words.  Every value is widened exactly (float or int32 -> double), so its square is
 // exact as well.
+// eb / ea: the per-episode records (EpisodeBuf above; the words table is in hftlob.h) and the agent's row
+// index env * n_agents + agent in them.  At an episode's last step (`all`) the lanes that hold the
+// values the accumulators add store them as record i, the agent's completed-episode count before this
+// step: lane 33's loaded word 1, made wave-uniform.  Lane 34 holds the episode's reward sum, lane 35
+// its length, lanes 40..63 the info words.  A count outside 0 .. cap - 1 writes nothing, and neither
+// does a launch without a buffer (rows == nullptr).
 DEV void tally_store(double* row, const TallyLane& t, float rew, const i32 (&iw)[HFTLOB_INFO_AGENT_WORDS], u32 f32,
-                     bool all) {
+                     bool all, kep_t* eb, size_t ea) {
     const int l = lane_id();
     const int k = l < 25 ? l - 1 : l - 40;  // the quantity lanes' info word (lane 0: the reward)
     i32 v = 0;
@@ -3429,10 +3446,22 @@ DEV void tally_store(double* row, const TallyLane& t, float rew, const i32 (&iw)
         else if ((h & 1) == 0) a = all ? t.a + run : t.a;   // completed episodes: sums
         else a = all ? t.a + run * run : t.a;               // and their squares
         row[h] = a;
+        x = run;  // (lanes 34 / 35: the episode's reward sum / length, for its record)
     } else if ((l < 25) | ((l >= 40) & all)) {
         const int w = tally_word(l);
         row[w] = t.a + x;
         row[w + 1] = t.b + x * x;
+    }
+    double* const ep = all ? eb->rows : nullptr;  // (wave-uniform; read only at an episode's end)
+    if (ep) {
+        const int ep_cap = eb->cap;
+        const double n = __longlong_as_double(
+            (long long)(((unsigned long long)(u32)rdl((i32)((unsigned long long)__double_as_longlong(t.a) >> 32), 33) << 32) |
+                        (u32)rdl((i32)(u32)__double_as_longlong(t.a), 33)));
+        if ((n >= 0.0) & (n < (double)ep_cap)) {
+            double* rec = ep + (ea * ep_cap + (size_t)(int)n) * HFTLOB_EPISODE_WORDS;
+            if ((l == 34) | (l == 35) | (l >= 40)) rec[l < 40 ? l - 34 : l - 38] = x;
+        }
     }
 }
 // NFIX > 0: nOrders == nTrades == NFIX known at compile time (the reference's
@@ -3472,7 +3501,7 @@ DEV bool env_step_dev(const hftlob_env_cfg& c_rt, int key_n, int ek, int e, cons
                       i32* __restrict__ info_out, i32* __restrict__ obs_raw_out, i32* __restrict__ msgs_out,
                       i32* __restrict__ debug_out, i32* lds, bool resident, bool keep, u32& fl_carry,
                       const i32* pre_keys = nullptr, bool emit_rt = true, double* __restrict__ stats = nullptr,
-                      int act_e = -1, i32 drawn = 0) {
+                      int act_e = -1, i32 drawn = 0, kep_t* eb = nullptr) {
     const hftlob_env_cfg& c = baked_cfg<BAKED>(c_rt);
     constexpr int UNR = baked_unroll<BAKED>();
     const bool emit = !QUIET && emit_rt;
@@ -4031,7 +4060,8 @@ DEV bool env_step_dev(const hftlob_env_cfg& c_rt, int key_n, int ek, int e, cons
 #ifndef HFTLOB_KO_TALLY
                 if constexpr (TALLY)
                     tally_store(stats + ((size_t)e * c.n_agents + ag) * HFTLOB_EVAL_WORDS, tl, rew, iw,
-                                tc.kind == HFTLOB_AGENT_MM ? INFO_F32_MM : INFO_F32_EXE, all);
+                                tc.kind == HFTLOB_AGENT_MM ? INFO_F32_MM : INFO_F32_EXE, all, eb,
+                                (size_t)e * c.n_agents + ag);
 #endif
                 if (emit & (l == 0)) {
                     rew_out[(size_t)e * c.n_agents + ag] = rew;
@@ -4263,6 +4293,10 @@ struct RolloutStep {
     u32 fl;  // (env_step_dev's flags word, carried from step to step)
     Balance bal;
     DEV const hftlob_env_cfg& cfg() const { return *(const hftlob_env_cfg*)cp; }
+    // (the evaluation kernels: their EpisodeBuf argument, in the kernarg segment after the config and n_env)
+    DEV kep_t* episode_buf() const {
+        return (kep_t*)((const __attribute__((address_space(4))) char*)cp + EPISODE_BUF_KERNARG);
+    }
     DEV bool in_lds() const { return NFIX > 0 && resident; }
     DEV bool keep() const { return NFIX > 0 && t + 1 < n_steps; }
     DEV void stepped(bool reset) { resident = uni(!reset) != 0; }
@@ -4452,9 +4486,11 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout_actions(hftlob_env_cfg c,
 // [HFTLOB_EVAL_WORDS], in/out) without an observation or an output store; the last step emits to
 // `out` as per_step = 0 does and is tallied as well.  The state and `out` are bit for bit those of
 // k_env_rollout_actions with per_step = 0.  fixed: `actions` is one row [action_words], read for
-// every env and step.
+// every env and step.  eb: the per-episode records' buffer (EpisodeBuf, hftlob_env_rollout_eval_episodes), or
+// {nullptr, 0}; the kernel body never names it: the tally reads it from the kernarg segment
+// (RolloutStep::episode_buf, tally_store).
 template <int S, int NFIX, bool RC, bool RA = false>
-__global__ __launch_bounds__(64, 4) void k_env_rollout_eval(hftlob_env_cfg c, int n_env, int n_steps, int fixed,
+__global__ __launch_bounds__(64, 4) void k_env_rollout_eval(hftlob_env_cfg c, int n_env, EpisodeBuf eb, int n_steps, int fixed,
                                                          const u32* __restrict__ keys,
                                                          const i32* __restrict__ actions,
                                                          const i32* __restrict__ msg_data,
@@ -4476,7 +4512,7 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout_eval(hftlob_env_cfg c, in
             const_cast<i32*>(actions) + (fixed ? (size_t)0 : (size_t)t * n_env * cc.action_words), s.md, s.is, s.st, out.obs,
             out.rewards, out.done_all, out.dones, ox ? out.info : nullptr, ox ? out.obs_raw : nullptr,
             ox ? out.msgs : nullptr, ox ? out.debug : nullptr, lds, s.in_lds(), s.keep(), s.fl, nullptr, !QT, s.sp,
-            fixed ? 0 : -1);
+            fixed ? 0 : -1, 0, s.episode_buf());
         s.stepped(reset);
         s.balance();
     });
@@ -4495,7 +4531,7 @@ struct DrawMasks {
     u32 m[HFTLOB_MAX_TYPES];
 };
 template <int S, int NFIX, bool RC, bool RA = false>
-__global__ __launch_bounds__(64, 4) void k_env_rollout_eval_drawn(hftlob_env_cfg c, int n_env, int n_steps,
+__global__ __launch_bounds__(64, 4) void k_env_rollout_eval_drawn(hftlob_env_cfg c, int n_env, EpisodeBuf eb, int n_steps,
                                                                const u32* __restrict__ keys,
                                                                const u32* __restrict__ draw_keys, DrawMasks am,
                                                                i32* __restrict__ actions_out,
@@ -4539,7 +4575,7 @@ __global__ __launch_bounds__(64, 4) void k_env_rollout_eval_drawn(hftlob_env_cfg
         const bool reset = env_step_dev<S, NFIX, RC, RA, QT, /*PK=*/0, /*TALLY=*/true, /*BAKED=*/-1, /*DRAWN=*/true>(
             cc, n_env, e, e, keys + (size_t)t * n_env * 2, false, mk, nullptr, s.md, s.is, s.st, out.obs, out.rewards,
             out.done_all, out.dones, ox ? out.info : nullptr, ox ? out.obs_raw : nullptr, ox ? out.msgs : nullptr,
-            ox ? out.debug : nullptr, lds, s.in_lds(), s.keep(), s.fl, nullptr, !QT, s.sp, -1, drawn);
+            ox ? out.debug : nullptr, lds, s.in_lds(), s.keep(), s.fl, nullptr, !QT, s.sp, -1, drawn, s.episode_buf());
         s.stepped(reset);
         s.balance();
     });
@@ -4601,9 +4637,9 @@ constexpr bool is_variant(int S, int NFIX, bool RC, bool RA) {
 #define HFTLOB_ROLL_ARGS hftlob_env_cfg, int, int, int, int, int, const u32*, u32*, i32*, const i32*, const i32*, i32*, \
                          hftlob_step_out
 #define HFTLOB_RACT_ARGS hftlob_env_cfg, int, int, int, const u32*, const i32*, const i32*, const i32*, i32*, hftlob_step_out
-#define HFTLOB_REVAL_ARGS hftlob_env_cfg, int, int, int, const u32*, const i32*, const i32*, const i32*, i32*, double*, \
-                          hftlob_step_out
-#define HFTLOB_REVALD_ARGS hftlob_env_cfg, int, int, const u32*, const u32*, DrawMasks, i32*, const i32*, const i32*, i32*, \
+#define HFTLOB_REVAL_ARGS hftlob_env_cfg, int, EpisodeBuf, int, int, const u32*, const i32*, const i32*, const i32*, i32*, \
+                          double*, hftlob_step_out
+#define HFTLOB_REVALD_ARGS hftlob_env_cfg, int, EpisodeBuf, int, const u32*, const u32*, DrawMasks, i32*, const i32*, const i32*, i32*, \
                            double*, hftlob_step_out
 #define HFTLOB_LISTED(SS, NF, RC, RA) static_assert(is_variant(SS, NF, RC, RA), "not in HFTLOB_VARIANTS");
 #define HFTLOB_STEP(P, SS, NF, RC, RA) \
@@ -5204,10 +5240,11 @@ int hftlob_env_rollout_actions(const hftlob_env_cfg* cfg, int n_env, int n_steps
                       n_steps, per_step, keys, actions, msg_data, init_states, state, *out);
 }
 
-int hftlob_env_rollout_eval(const hftlob_env_cfg* cfg, int n_env, int n_steps, const uint32_t* keys,
+// hftlob_env_rollout_eval and hftlob_env_rollout_eval_episodes: one launch, the second with the records' buffer
+static int env_rollout_eval(const hftlob_env_cfg* cfg, int n_env, int n_steps, const uint32_t* keys,
                             const int32_t* actions, int actions_fixed, const int32_t* msg_data,
                             const int32_t* init_states, int32_t* state, double* stats, const hftlob_step_out* out,
-                            void* stream) {
+                            double* episodes, int ep_cap, void* stream) {
     int rc = check_env(cfg);
     if (rc) return rc;
     // (the last step always emits and every step adds to stats: no empty call, unlike the rollouts above)
@@ -5215,13 +5252,39 @@ int hftlob_env_rollout_eval(const hftlob_env_cfg* cfg, int n_env, int n_steps, c
     if (!keys || !actions || !msg_data || !init_states || !state || !stats || !out) return fail(HFTLOB_ENULL, "null array");
     if ((rc = check_out(out))) return rc;
     return env_launch(cfg, n_env, stream, LISTED_KERNEL(k_env_rollout_eval),
-                      n_steps, actions_fixed != 0 ? 1 : 0, keys, actions, msg_data, init_states, state, stats, *out);
+                      EpisodeBuf{episodes, ep_cap}, n_steps, actions_fixed != 0 ? 1 : 0, keys, actions, msg_data, init_states,
+                      state, stats, *out);
 }
 
-int hftlob_env_rollout_eval_drawn(const hftlob_env_cfg* cfg, int n_env, int n_steps, const uint32_t* keys,
+int hftlob_env_rollout_eval(const hftlob_env_cfg* cfg, int n_env, int n_steps, const uint32_t* keys,
+                            const int32_t* actions, int actions_fixed, const int32_t* msg_data,
+                            const int32_t* init_states, int32_t* state, double* stats, const hftlob_step_out* out,
+                            void* stream) {
+    return env_rollout_eval(cfg, n_env, n_steps, keys, actions, actions_fixed, msg_data, init_states, state, stats, out,
+                            nullptr, 0, stream);
+}
+
+// the records' buffer of the _episodes entry points: both given, or the call is refused
+static int check_episodes(const double* episodes, int ep_cap) {
+    if (!episodes) return fail(HFTLOB_EINVAL, "episodes is NULL (the entry point without _episodes keeps no records)");
+    if (ep_cap < 1) return fail(HFTLOB_EINVAL, "ep_cap must be >= 1");
+    return HFTLOB_OK;
+}
+
+int hftlob_env_rollout_eval_episodes(const hftlob_env_cfg* cfg, int n_env, int n_steps, const uint32_t* keys,
+                                     const int32_t* actions, int actions_fixed, const int32_t* msg_data,
+                                     const int32_t* init_states, int32_t* state, double* stats,
+                                     const hftlob_step_out* out, double* episodes, int ep_cap, void* stream) {
+    const int rc = check_episodes(episodes, ep_cap);
+    if (rc) return rc;
+    return env_rollout_eval(cfg, n_env, n_steps, keys, actions, actions_fixed, msg_data, init_states, state, stats, out,
+                            episodes, ep_cap, stream);
+}
+
+static int env_rollout_eval_drawn(const hftlob_env_cfg* cfg, int n_env, int n_steps, const uint32_t* keys,
                                   const uint32_t* draw_keys, const uint32_t* allowed, int32_t* actions_out,
                                   const int32_t* msg_data, const int32_t* init_states, int32_t* state, double* stats,
-                                  const hftlob_step_out* out, void* stream) {
+                                  const hftlob_step_out* out, double* episodes, int ep_cap, void* stream) {
     int rc = check_env(cfg);
     if (rc) return rc;
     if (n_env < 1 || n_steps < 1) return fail(HFTLOB_ESHAPE, "n_env and n_steps must be >= 1");
@@ -5244,7 +5307,27 @@ int hftlob_env_rollout_eval_drawn(const hftlob_env_cfg* cfg, int n_env, int n_st
         am.m[t] = allowed[t];
     }
     return env_launch(cfg, n_env, stream, LISTED_KERNEL(k_env_rollout_eval_drawn),
-                      n_steps, keys, draw_keys, am, actions_out, msg_data, init_states, state, stats, *out);
+                      EpisodeBuf{episodes, ep_cap}, n_steps, keys, draw_keys, am, actions_out, msg_data, init_states, state,
+                      stats, *out);
+}
+
+int hftlob_env_rollout_eval_drawn(const hftlob_env_cfg* cfg, int n_env, int n_steps, const uint32_t* keys,
+                                  const uint32_t* draw_keys, const uint32_t* allowed, int32_t* actions_out,
+                                  const int32_t* msg_data, const int32_t* init_states, int32_t* state, double* stats,
+                                  const hftlob_step_out* out, void* stream) {
+    return env_rollout_eval_drawn(cfg, n_env, n_steps, keys, draw_keys, allowed, actions_out, msg_data, init_states,
+                                  state, stats, out, nullptr, 0, stream);
+}
+
+int hftlob_env_rollout_eval_drawn_episodes(const hftlob_env_cfg* cfg, int n_env, int n_steps, const uint32_t* keys,
+                                           const uint32_t* draw_keys, const uint32_t* allowed, int32_t* actions_out,
+                                           const int32_t* msg_data, const int32_t* init_states, int32_t* state,
+                                           double* stats, const hftlob_step_out* out, double* episodes, int ep_cap,
+                                           void* stream) {
+    const int rc = check_episodes(episodes, ep_cap);
+    if (rc) return rc;
+    return env_rollout_eval_drawn(cfg, n_env, n_steps, keys, draw_keys, allowed, actions_out, msg_data, init_states,
+                                  state, stats, out, episodes, ep_cap, stream);
 }
 #undef LISTED_KERNEL
 

@@ -51,11 +51,13 @@ class PolicyGroup(C.Structure):
 LIB_PATH = os.environ.get("HFTLOB_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhftlob.so")
 ABI_VERSION = 8
 EVAL_WORDS = 106  # HFTLOB_EVAL_WORDS: doubles per agent in hftlob_env_rollout_eval's stats (the table is in hftlob.h)
+EPISODE_WORDS = 26  # HFTLOB_EPISODE_WORDS: doubles per (env, agent, completed episode) in the episodes buffers
 EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob_book_depth",
            "hftlob_book_process_depth", "hftlob_env_reset",
            "hftlob_env_step", "hftlob_env_step_sampled", "hftlob_env_rollout_sampled", "hftlob_rollout_prepare",
            "hftlob_env_rollout_actions", "hftlob_env_rollout_eval", "hftlob_eval_tally",
            "hftlob_draw_actions", "hftlob_env_rollout_eval_drawn",
+           "hftlob_env_rollout_eval_episodes", "hftlob_env_rollout_eval_drawn_episodes", "hftlob_eval_tally_episodes",
            "hftlob_env_lds_bytes", "hftlob_env_launch_info", "hftlob_env_baked_id", "hftlob_set_baked",
            "hftlob_sample_actions", "hftlob_split_keys", "hftlob_gru_scan_fwd", "hftlob_gru_scan_bwd",
            "hftlob_gru_scan_fwd_grouped", "hftlob_gru_scan_bwd_grouped",
@@ -107,6 +109,13 @@ def lib() -> C.CDLL:
     L.hftlob_env_rollout_eval_drawn.argtypes = [C.POINTER(EnvCfg), i32, i32, vp, vp, C.POINTER(C.c_uint32), vp, vp, vp, vp,
                                                 vp, C.POINTER(StepOut), vp]
     L.hftlob_env_rollout_eval_drawn.restype = i32
+    # the three with per-episode records: the sibling's arguments, then `episodes, ep_cap` before the stream
+    L.hftlob_env_rollout_eval_episodes.argtypes = L.hftlob_env_rollout_eval.argtypes[:-1] + [vp, i32, vp]
+    L.hftlob_env_rollout_eval_episodes.restype = i32
+    L.hftlob_eval_tally_episodes.argtypes = L.hftlob_eval_tally.argtypes[:-1] + [vp, i32, vp]
+    L.hftlob_eval_tally_episodes.restype = i32
+    L.hftlob_env_rollout_eval_drawn_episodes.argtypes = L.hftlob_env_rollout_eval_drawn.argtypes[:-1] + [vp, i32, vp]
+    L.hftlob_env_rollout_eval_drawn_episodes.restype = i32
     L.hftlob_rollout_prepare.argtypes = [i32, vp]
     L.hftlob_rollout_prepare.restype = i32
     L.hftlob_env_lds_bytes.argtypes = [C.POINTER(EnvCfg)]

@@ -631,7 +631,8 @@ class MARLEnv:
         return torch.cat([x.to(self.device).reshape(-1) for x in parts]).contiguous()
 
     def rollout_eval(self, key: torch.Tensor, state: MultiAgentState, actions, params: MultiAgentParams,
-                     stats: Optional[torch.Tensor] = None, fixed: bool = False):
+                     stats: Optional[torch.Tensor] = None, fixed: bool = False,
+                     episodes: Optional[torch.Tensor] = None):
         """:meth:`rollout` with ``per_step=False`` whose every step also folds the agents' rewards
         and info words into ``stats`` (hftlob_env_rollout_eval; the words of a row are listed in
         include/hftlob.h and named by :class:`hftlob.evaluate.EvalStats`): the evaluation loop of the
@@ -642,7 +643,12 @@ class MARLEnv:
         ``fixed=True`` ONE action row used for every env and step: int32 [action_words], or the
         per-type list without the T and E axes.  stats: float64 [E, num_agents, EVAL_WORDS] on this
         env's device, added to in place (so an evaluation can be cut into calls); None allocates a
-        zeroed one."""
+        zeroed one.
+        episodes: a contiguous float64 [E, num_agents, cap, EPISODE_WORDS] tensor on this env's device
+        for the per-episode records (hftlob_env_rollout_eval_episodes; :class:`hftlob.evaluate.EpisodeLog`
+        reads them): the record of an agent's i-th completed episode, counted by its stats word 1, goes
+        to slot i if i < cap, and the other slots are left as they are.  It is filled in place and
+        appended to the returned tuple.  None keeps no records (the call and its tuple are as above)."""
         if key.dtype not in (torch.int32, torch.uint32) or key.dim() != 3 or key.shape[2] != 2:
             raise ValueError("key must be a uint32/int32 tensor [T, E, 2] (one threefry key per step and env)")
         T, E = int(key.shape[0]), int(key.shape[1])
@@ -657,16 +663,34 @@ class MARLEnv:
         elif (not isinstance(stats, torch.Tensor) or stats.dtype != torch.float64 or tuple(stats.shape) != shape
               or stats.device != state.buf.device or not stats.is_contiguous()):
             raise ValueError(f"stats must be a contiguous float64 {list(shape)} tensor on {state.buf.device}")
+        cap = self._episodes_cap(episodes, E, state.buf.device)
         keys = key.to(self.device).contiguous()
         o = self._outputs(E)
-        self._abi("hftlob_env_rollout_eval", C.byref(self.cfg_c), E, T, _lib.ptr(keys), _lib.ptr(acts), int(fixed),
-                  _lib.ptr(params.loaded_params.message_data), _lib.ptr(params.loaded_params.init_states_array),
-                  _lib.ptr(state.buf), _lib.ptr(stats), C.byref(o["struct"]))
-        return self._results(o, state, E) + (stats,)
+        if episodes is None:
+            self._abi("hftlob_env_rollout_eval", C.byref(self.cfg_c), E, T, _lib.ptr(keys), _lib.ptr(acts), int(fixed),
+                      _lib.ptr(params.loaded_params.message_data), _lib.ptr(params.loaded_params.init_states_array),
+                      _lib.ptr(state.buf), _lib.ptr(stats), C.byref(o["struct"]))
+            return self._results(o, state, E) + (stats,)
+        self._abi("hftlob_env_rollout_eval_episodes", C.byref(self.cfg_c), E, T, _lib.ptr(keys), _lib.ptr(acts),
+                  int(fixed), _lib.ptr(params.loaded_params.message_data),
+                  _lib.ptr(params.loaded_params.init_states_array), _lib.ptr(state.buf), _lib.ptr(stats),
+                  C.byref(o["struct"]), _lib.ptr(episodes), cap)
+        return self._results(o, state, E) + (stats, episodes)
+
+    def _episodes_cap(self, episodes, E: int, dev) -> int:
+        """the cap of a checked ``episodes`` buffer of the evaluation launches (0 for None)"""
+        if episodes is None:
+            return 0
+        if (not isinstance(episodes, torch.Tensor) or episodes.dtype != torch.float64 or episodes.dim() != 4
+                or tuple(episodes.shape[:2]) != (E, self.num_agents) or episodes.shape[3] != _lib.EPISODE_WORDS
+                or episodes.shape[2] < 1 or episodes.device != dev or not episodes.is_contiguous()):
+            raise ValueError(f"episodes must be a contiguous float64 [{E}, {self.num_agents}, cap, {_lib.EPISODE_WORDS}] "
+                             f"tensor on {dev} with cap (ep_cap) >= 1")
+        return int(episodes.shape[2])
 
     def rollout_eval_drawn(self, key: torch.Tensor, state: MultiAgentState, draw_keys: torch.Tensor, allowed,
                            params: MultiAgentParams, stats: Optional[torch.Tensor] = None,
-                           actions_out: Optional[torch.Tensor] = None):
+                           actions_out: Optional[torch.Tensor] = None, episodes: Optional[torch.Tensor] = None):
         """:meth:`rollout_eval` whose actions are drawn inside the launch (hftlob_env_rollout_eval_drawn):
         at every step each agent of type i takes the smallest allowed action that maximises its
         Gumbel noise under that step's key of the type, :func:`hftlob.evaluate.draw_actions` of the
@@ -677,7 +701,8 @@ class MARLEnv:
         allowed: one bit mask per agent type (host ints; bit a set = action a may be drawn; a mask
         of one bit is a fixed action).  Every type must have a Discrete space of at most 32 actions
         and the env partitionable keys.  actions_out: int32 [T, E, action_words] on the device to
-        receive the drawn actions, or None."""
+        receive the drawn actions, or None.  episodes: as :meth:`rollout_eval` takes it
+        (hftlob_env_rollout_eval_drawn_episodes)."""
         if key.dtype not in (torch.int32, torch.uint32) or key.dim() != 3 or key.shape[2] != 2:
             raise ValueError("key must be a uint32/int32 tensor [T, E, 2] (one threefry key per step and env)")
         T, E = int(key.shape[0]), int(key.shape[1])
@@ -704,13 +729,20 @@ class MARLEnv:
         elif (not isinstance(stats, torch.Tensor) or stats.dtype != torch.float64 or tuple(stats.shape) != shape
               or stats.device != dev or not stats.is_contiguous()):
             raise ValueError(f"stats must be a contiguous float64 {list(shape)} tensor on {dev}")
+        cap = self._episodes_cap(episodes, E, dev)
         keys = key.to(self.device).contiguous()
         o = self._outputs(E)
-        self._abi("hftlob_env_rollout_eval_drawn", C.byref(self.cfg_c), E, T, _lib.ptr(keys),
+        if episodes is None:
+            self._abi("hftlob_env_rollout_eval_drawn", C.byref(self.cfg_c), E, T, _lib.ptr(keys),
+                      _lib.ptr(draw_keys), (C.c_uint32 * n_types)(*masks), _lib.ptr(actions_out),
+                      _lib.ptr(params.loaded_params.message_data), _lib.ptr(params.loaded_params.init_states_array),
+                      _lib.ptr(state.buf), _lib.ptr(stats), C.byref(o["struct"]))
+            return self._results(o, state, E) + (stats,)
+        self._abi("hftlob_env_rollout_eval_drawn_episodes", C.byref(self.cfg_c), E, T, _lib.ptr(keys),
                   _lib.ptr(draw_keys), (C.c_uint32 * n_types)(*masks), _lib.ptr(actions_out),
                   _lib.ptr(params.loaded_params.message_data), _lib.ptr(params.loaded_params.init_states_array),
-                  _lib.ptr(state.buf), _lib.ptr(stats), C.byref(o["struct"]))
-        return self._results(o, state, E) + (stats,)
+                  _lib.ptr(state.buf), _lib.ptr(stats), C.byref(o["struct"]), _lib.ptr(episodes), cap)
+        return self._results(o, state, E) + (stats, episodes)
 
     def _results_steps(self, o, state, T: int, E: int):
         """_results of per-step buffers [T, E, ...]: a leading [T] on obs / rewards / dones."""

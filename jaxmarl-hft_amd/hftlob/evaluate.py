@@ -30,7 +30,14 @@ into per-agent accumulators instead of writing a trajectory.
   launch (``--uniform-actions 1+2+3,all``); :func:`evaluate_policy` and
   :func:`evaluate_combinations` take a ``Uniform`` where they take a fixed action.
 
-Plotting (the rest of baseline_eval/) is not covered.
+* Per-episode records: the launches above also write one record per (env, agent, completed episode)
+  into an ``episodes`` buffer (``max_episodes=`` / ``episodes=``; include/hftlob.h lists the words), and
+  :class:`EpisodeLog` reads it: the episode rewards ``[episodes, agents]``, lengths and end-of-episode
+  info fields, their quantiles, tail means and histograms, and ``EpisodeLog.save`` /
+  :func:`save_combinations` write the files baseline_eval/plotting_combinations.py loads
+  (``--episodes-out PATH``).
+
+Plotting itself (the rest of baseline_eval/) is not covered.
 """
 from __future__ import annotations
 
@@ -47,7 +54,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import EVAL_WORDS
+from ._lib import EPISODE_WORDS, EVAL_WORDS
 from .layout import AGENT_MM, INFO_AGENT_WORDS, INFO_EXE, INFO_MM, INFO_WORLD_WORDS
 
 # words of an agent's row (include/hftlob.h, hftlob_env_rollout_eval)
@@ -56,6 +63,9 @@ W_STEP_Q = 8            # + 2q, + 2q + 1: quantity q (0 the reward, 1 + k info w
 W_END_INFO = 58         # + 2k, + 2k + 1: info word k at each episode's last step
 N_QUANT = 1 + INFO_AGENT_WORDS
 assert W_STEP_Q + 2 * N_QUANT == W_END_INFO and W_END_INFO + 2 * INFO_AGENT_WORDS == EVAL_WORDS
+# words of an episode's record (include/hftlob.h, hftlob_env_rollout_eval_episodes)
+R_SUM, R_LEN, R_INFO = 0, 1, 2      # the reward sum, the length, + k: info word k at the last step
+assert R_INFO + INFO_AGENT_WORDS == EPISODE_WORDS
 
 
 def _float_words(layout) -> torch.Tensor:
@@ -67,8 +77,15 @@ def _float_words(layout) -> torch.Tensor:
     return torch.tensor(rows, dtype=torch.bool)
 
 
+def _check_cap(cap) -> int:
+    if isinstance(cap, bool) or not isinstance(cap, int) or cap < 1:
+        raise ValueError(f"max_episodes (ep_cap) must be an int >= 1, got {cap!r}")
+    return cap
+
+
 def reduce_steps(rewards, info_words: torch.Tensor, done_all: torch.Tensor, layout,
-                 stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 stats: Optional[torch.Tensor] = None, episodes: Optional[torch.Tensor] = None,
+                 max_episodes: Optional[int] = None):
     """The accumulators of hftlob_env_rollout_eval from per-step outputs, as a sequential float64
     loop over the steps (every word is one plain sum in step order; a widened float32 / int32
     squares exactly), on the inputs' device.
@@ -77,7 +94,15 @@ def reduce_steps(rewards, info_words: torch.Tensor, done_all: torch.Tensor, layo
     info_words: the raw info record, int32 [T, E, info_words] (``env.last_info_words`` of a
     per_step rollout, reshaped; [T * E, info_words] is accepted).  done_all: bool [T, E].
     layout: the env's ``EnvLayout``.  stats: float64 [E, n_agents, EVAL_WORDS] to continue from
-    (not modified); None starts from zeros.  Returns the new stats tensor."""
+    (not modified); None starts from zeros.  Returns the new stats tensor.
+
+    With ``max_episodes`` (the cap) or ``episodes`` (float64 [E, n_agents, cap, EPISODE_WORDS] to continue
+    from, not modified; with the cap alone it starts from zeros) the per-episode records are kept as
+    well, and the return value is ``(stats, episodes)``.  At a step whose done_all is set, agent a's
+    record is the running reward sum and length as they are added to words 4 and 6, then the step's 24
+    info words as they are added to words 58 + 2k; it goes to slot i = word 1 before the step's
+    increment, iff 0 <= i < cap.  Every other slot keeps what it held.  This is the definition the HIP
+    launches are held to bit for bit."""
     if not isinstance(rewards, torch.Tensor):
         rewards = torch.cat([x.reshape(x.shape[0], x.shape[1], -1) for x in rewards], dim=2)
     T, E, A = rewards.shape
@@ -91,6 +116,15 @@ def reduce_steps(rewards, info_words: torch.Tensor, done_all: torch.Tensor, layo
     st = torch.zeros((E, A, EVAL_WORDS), dtype=torch.float64, device=dev) if stats is None else stats.clone()
     if tuple(st.shape) != (E, A, EVAL_WORDS) or st.dtype != torch.float64 or st.device != dev:
         raise ValueError(f"stats must be float64 [{E}, {A}, {EVAL_WORDS}] on {dev}")
+    ep = None
+    if episodes is not None or max_episodes is not None:
+        if episodes is not None and (not isinstance(episodes, torch.Tensor) or episodes.dim() != 4):
+            raise ValueError(f"episodes must be float64 [{E}, {A}, cap, {EPISODE_WORDS}] on {dev}")
+        cap = _check_cap(max_episodes if max_episodes is not None else int(episodes.shape[2]))
+        ep = torch.zeros((E, A, cap, EPISODE_WORDS), dtype=torch.float64, device=dev) if episodes is None \
+            else episodes.clone()
+        if tuple(ep.shape) != (E, A, cap, EPISODE_WORDS) or ep.dtype != torch.float64 or ep.device != dev:
+            raise ValueError(f"episodes must be float64 [{E}, {A}, {cap}, {EPISODE_WORDS}] on {dev}")
     iw = info_words.reshape(T, E, layout.info_words)[:, :, INFO_WORLD_WORDS:INFO_WORLD_WORDS + A * INFO_AGENT_WORDS]
     iw = iw.reshape(T, E, A, INFO_AGENT_WORDS).contiguous()
     isf = _float_words(layout).to(dev)
@@ -102,6 +136,14 @@ def reduce_steps(rewards, info_words: torch.Tensor, done_all: torch.Tensor, layo
     zero = torch.zeros((), dtype=torch.float64, device=dev)
     for t in range(T):
         d = done[t][:, None]                                   # [E, 1] over the agents
+        if ep is not None:
+            # the record of every (env, agent) whose episode ends here, at the count before this step
+            i = st[:, :, W_EPISODES]
+            w = d & (i >= 0) & (i < cap)                       # [E, A]
+            rec = torch.cat([(st[:, :, W_RUN_SUM] + x[t, :, :, 0])[..., None], (st[:, :, W_RUN_LEN] + 1.0)[..., None],
+                             x[t, :, :, 1:]], dim=2)           # [E, A, EPISODE_WORDS]
+            e_i, a_i = torch.nonzero(w, as_tuple=True)
+            ep[e_i, a_i, i[e_i, a_i].to(torch.int64)] = rec[e_i, a_i]
         st[:, :, W_STEPS] += 1.0
         st[:, :, W_EPISODES] += d.to(torch.float64)
         run_sum = st[:, :, W_RUN_SUM] + x[t, :, :, 0]
@@ -117,7 +159,7 @@ def reduce_steps(rewards, info_words: torch.Tensor, done_all: torch.Tensor, layo
         st[:, :, W_END_INFO::2] = torch.where(d3, st[:, :, W_END_INFO::2] + x[t, :, :, 1:], st[:, :, W_END_INFO::2])
         st[:, :, W_END_INFO + 1::2] = torch.where(d3, st[:, :, W_END_INFO + 1::2] + x2[t, :, :, 1:],
                                                   st[:, :, W_END_INFO + 1::2])
-    return st
+    return st if ep is None else (st, ep)
 
 
 def _float_word_masks(layout):
@@ -126,24 +168,43 @@ def _float_word_masks(layout):
     return (C.c_uint32 * len(rows))(*[sum(1 << k for k, isf in enumerate(r) if isf) for r in rows])
 
 
-def _tally_launch(rewards, info_words, done_all, masks, info_w: int, stats) -> None:
-    """hftlob_eval_tally on checked device tensors ([T, E, A], [T, E, info_w], [T, E] bytes), adding to stats"""
+def _tally_launch(rewards, info_words, done_all, masks, info_w: int, stats, episodes=None) -> None:
+    """hftlob_eval_tally on checked device tensors ([T, E, A], [T, E, info_w], [T, E] bytes), adding to stats;
+    with ``episodes`` ([E, A, cap, EPISODE_WORDS]) hftlob_eval_tally_episodes, which also writes the records"""
     T, E, A = rewards.shape
     dev = rewards.device
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().hftlob_eval_tally(E, A, T, info_w, _lib.ptr(rewards), _lib.ptr(info_words),
-                                                _lib.ptr(done_all), masks, _lib.ptr(stats),
-                                                _lib.stream_ptr(device=dev)))
+        if episodes is None:
+            _lib.check(_lib.lib().hftlob_eval_tally(E, A, T, info_w, _lib.ptr(rewards), _lib.ptr(info_words),
+                                                    _lib.ptr(done_all), masks, _lib.ptr(stats),
+                                                    _lib.stream_ptr(device=dev)))
+        else:
+            _lib.check(_lib.lib().hftlob_eval_tally_episodes(E, A, T, info_w, _lib.ptr(rewards), _lib.ptr(info_words),
+                                                             _lib.ptr(done_all), masks, _lib.ptr(stats),
+                                                             _lib.ptr(episodes), int(episodes.shape[2]),
+                                                             _lib.stream_ptr(device=dev)))
+
+
+def _check_episodes(episodes, E: int, A: int, dev) -> None:
+    """a caller's ``episodes`` buffer of a launch: contiguous float64 [E, A, cap >= 1, EPISODE_WORDS] on dev"""
+    if (not isinstance(episodes, torch.Tensor) or episodes.dtype != torch.float64 or episodes.dim() != 4
+            or tuple(episodes.shape[:2]) != (E, A) or episodes.shape[3] != EPISODE_WORDS or episodes.shape[2] < 1
+            or episodes.device != dev or not episodes.is_contiguous()):
+        raise ValueError(f"episodes must be a contiguous float64 [{E}, {A}, cap, {EPISODE_WORDS}] tensor on {dev} "
+                         "with cap (ep_cap) >= 1")
 
 
 def tally_steps(rewards, info_words: torch.Tensor, done_all: torch.Tensor, layout,
-                stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+                stats: Optional[torch.Tensor] = None, episodes: Optional[torch.Tensor] = None):
     """:func:`reduce_steps` as one launch of hftlob_eval_tally (csrc/eval_tally.hip) on torch's current
     stream: the same arguments, the same bits.  The tensors must be on a GPU (there is no other path);
     done_all is bool or uint8 [T, E].  Unlike reduce_steps a given ``stats`` (contiguous float64
     [E, n_agents, EVAL_WORDS] on that device) is continued IN PLACE; None starts from zeros.  Returns
     the stats tensor.  Nothing is allocated beyond a missing ``stats`` and a per-type rewards list's
-    concatenation, and nothing synchronises."""
+    concatenation, and nothing synchronises.
+    episodes: a contiguous float64 [E, n_agents, cap, EPISODE_WORDS] tensor on that device for the
+    per-episode records (hftlob_eval_tally_episodes; :func:`reduce_steps` defines them), filled IN PLACE;
+    the return value is then ``(stats, episodes)``."""
     if not isinstance(rewards, torch.Tensor):
         rewards = torch.cat([x.reshape(x.shape[0], x.shape[1], -1) for x in rewards], dim=2)
     if rewards.dim() != 3 or rewards.shape[2] != len(layout.agent_kinds) or rewards.dtype != torch.float32:
@@ -166,11 +227,13 @@ def tally_steps(rewards, info_words: torch.Tensor, done_all: torch.Tensor, layou
     elif (not isinstance(stats, torch.Tensor) or tuple(stats.shape) != (E, A, EVAL_WORDS) or stats.dtype != torch.float64
           or stats.device != dev or not stats.is_contiguous()):
         raise ValueError(f"stats must be a contiguous float64 [{E}, {A}, {EVAL_WORDS}] tensor on {dev}")
+    if episodes is not None:
+        _check_episodes(episodes, E, A, dev)
     if done_all.dtype == torch.bool:
         done_all = done_all.view(torch.uint8)
     _tally_launch(rewards.contiguous(), info_words.contiguous(), done_all.contiguous(), _float_word_masks(layout),
-                  layout.info_words, stats)
-    return stats
+                  layout.info_words, stats, episodes)
+    return stats if episodes is None else (stats, episodes)
 
 
 def _mean_std(n: float, s: float, s2: float) -> Dict[str, float]:
@@ -245,6 +308,168 @@ class EvalStats:
                           "episode_reward": self.episode_reward(t), "episode_length": self.episode_length(t),
                           "info_at_episode_end": self.info_at_episode_end(t)})
         return {"total_dones": self.total_dones(), "types": types}
+
+
+class EpisodeLog:
+    """The per-episode records of an evaluation read as arrays: ``episodes`` (float64 [E, n_agents, cap,
+    EPISODE_WORDS], as the launches or :func:`reduce_steps` filled it from zeroed ``stats``) with the
+    ``stats`` tensor that counts them.  Env e completed ``stats[e, 0, 1]`` episodes (all agents of an env
+    share done_all, so they share the count), of which the first ``cap`` have a record; the others were
+    dropped.  A row of the arrays below is one episode: the (env, episode index) pairs in env-major
+    order.  ``t`` is an agent type; a type's values are those of all its agents.  Everything is float64
+    on the CPU."""
+
+    def __init__(self, episodes: torch.Tensor, stats: torch.Tensor, layout):
+        A = len(layout.agent_kinds)
+        if not isinstance(episodes, torch.Tensor) or episodes.dim() != 4 or episodes.shape[1] != A \
+                or episodes.shape[3] != EPISODE_WORDS or episodes.dtype != torch.float64:
+            raise ValueError(f"episodes must be float64 [E, {A}, cap, {EPISODE_WORDS}]")
+        E, cap = int(episodes.shape[0]), int(episodes.shape[2])
+        if not isinstance(stats, torch.Tensor) or tuple(stats.shape) != (E, A, EVAL_WORDS) or stats.dtype != torch.float64:
+            raise ValueError(f"stats must be float64 [{E}, {A}, {EVAL_WORDS}]")
+        self.layout = layout
+        self.cap = cap
+        self.n_types = max(layout.agent_types) + 1
+        done = stats[:, 0, W_EPISODES].cpu().to(torch.int64)
+        self.count = done.clamp(0, cap)                                   # [E]: episodes with a record
+        self.dropped = int((done - self.count).clamp(min=0).sum().item())   # completed, but past the cap
+        keep = torch.arange(cap)[None, :] < self.count[:, None]           # [E, cap]
+        self._rec = episodes.cpu().permute(0, 2, 1, 3)[keep]              # [n_episodes, A, EPISODE_WORDS]
+        self.env = torch.nonzero(keep, as_tuple=True)[0]                  # [n_episodes]: each row's env
+
+    def __len__(self) -> int:
+        return int(self._rec.shape[0])
+
+    def _agents(self, t: int) -> List[int]:
+        ags = [a for a, ty in enumerate(self.layout.agent_types) if ty == t]
+        if not ags:
+            raise ValueError(f"no agent type {t}")
+        return ags
+
+    def fields(self, t: int) -> List[str]:
+        """the info field names of type t (layout.INFO_MM / INFO_EXE)"""
+        kind = self.layout.agent_kinds[self._agents(t)[0]]
+        return [n for n, _ in (INFO_MM if kind == AGENT_MM else INFO_EXE)]
+
+    def rewards(self) -> torch.Tensor:
+        """the episodes' reward sums [n_episodes, n_agents]: plotting_combinations.py's array of a configuration"""
+        return self._rec[:, :, R_SUM].clone()
+
+    def lengths(self) -> torch.Tensor:
+        """the episodes' lengths in steps [n_episodes] (the agents of an env share them)"""
+        return self._rec[:, 0, R_LEN].clone()
+
+    def field(self, t: int, name: str) -> torch.Tensor:
+        """info field ``name`` of type t at the episodes' last steps [n_episodes, the type's agents]"""
+        names = self.fields(t)
+        if name not in names:
+            raise ValueError(f"agent type {t} has no info field {name!r}; its fields: {names}")
+        return self._rec[:, self._agents(t), R_INFO + names.index(name)].clone()
+
+    def values(self, t: int, what: str = "reward") -> torch.Tensor:
+        """type t's values of ``what`` over all episodes and the type's agents, flat: "reward" (the
+        episode's reward sum), "length", or an info field at the episode's last step"""
+        if what == "reward":
+            return self._rec[:, self._agents(t), R_SUM].reshape(-1)
+        if what == "length":
+            return self._rec[:, self._agents(t), R_LEN].reshape(-1)
+        return self.field(t, what).reshape(-1)
+
+    def quantiles(self, t: int, qs: Sequence[float], what: str = "reward") -> torch.Tensor:
+        """``torch.quantile`` (linear interpolation) of the values in float64, [len(qs)]; NaN without episodes"""
+        v = self.values(t, what)
+        q = torch.as_tensor(list(qs), dtype=torch.float64)
+        if v.numel() == 0:
+            return torch.full_like(q, math.nan)
+        return torch.quantile(v, q)
+
+    def cvar(self, t: int, alpha: float, what: str = "reward") -> float:
+        """the mean of the worst (smallest) ``alpha`` share of the values: the ceil(alpha n) smallest of
+        n, at least one (the expected shortfall of the episode outcome); NaN without episodes"""
+        if not 0.0 < alpha <= 1.0:
+            raise ValueError(f"alpha must be in (0, 1], got {alpha}")
+        v = self.values(t, what)
+        if v.numel() == 0:
+            return math.nan
+        k = min(v.numel(), max(1, math.ceil(alpha * v.numel() - 1e-12)))
+        return float(torch.sort(v)[0][:k].mean().item())
+
+    def histogram(self, t: int, bins: int = 30, what: str = "reward") -> Tuple[torch.Tensor, torch.Tensor]:
+        """(counts float64 [bins], edges float64 [bins + 1]) of the finite values, ``bins`` equal bins
+        between their minimum and maximum (the plots' ``hist(all_rewards, bins=30)``)"""
+        v = self.values(t, what)
+        v = v[torch.isfinite(v)]
+        if v.numel() == 0:
+            return torch.zeros(bins, dtype=torch.float64), torch.linspace(0.0, 1.0, bins + 1, dtype=torch.float64)
+        return tuple(torch.histogram(v, bins=bins))
+
+    def summary(self, qs: Sequence[float] = (0.05, 0.25, 0.5, 0.75, 0.95), alpha: float = 0.05) -> dict:
+        """a JSON-able digest: the counts, and per agent type the episode reward's mean, extremes,
+        quantiles and tail mean, and the episode length's mean"""
+        types = []
+        for t in range(self.n_types):
+            r = self.values(t, "reward")
+            n = int(r.numel())
+            qv = self.quantiles(t, qs).tolist()
+            types.append({"values": n,
+                          "episode_reward": {"mean": float(r.mean().item()) if n else math.nan,
+                                             "min": float(r.min().item()) if n else math.nan,
+                                             "max": float(r.max().item()) if n else math.nan,
+                                             "quantiles": {str(q): v for q, v in zip(qs, qv)},
+                                             "cvar": {"alpha": alpha, "value": self.cvar(t, alpha)}},
+                          "episode_length": {"mean": float(self.values(t, "length").mean().item()) if n else math.nan}})
+        return {"episodes": len(self), "dropped": self.dropped, "cap": self.cap, "types": types}
+
+    def save(self, path: str, name: str = "Config") -> None:
+        """The episode rewards as configuration ``name`` of a file baseline_eval/plotting_combinations.py
+        loads; the format follows the suffix (.npz, .json, .pkl, .csv; :func:`save_combinations` has the
+        formats)."""
+        _save_reward_arrays(path, {name: self.rewards().numpy()})
+
+
+def _agent_columns(n_agents: int) -> List[str]:
+    """the CSV's agent columns: the reference's two names for two agents, Agent_i otherwise"""
+    return ["MarketMaker", "ExecutionAgent"] if n_agents == 2 else [f"Agent_{i}" for i in range(n_agents)]
+
+
+def _save_reward_arrays(path: str, arrays: Dict[str, np.ndarray]) -> None:
+    """{name: float64 [episodes, agents]} in the formats baseline_eval/plotting_combinations.py loads, by
+    the path's suffix: .npz (one array per name), .json (nested lists per name), .pkl (the pickled dict of
+    arrays), .csv (a row per name and episode: Configuration, Episode, then a column per agent)."""
+    suffix = os.path.splitext(path)[1].lower()
+    if suffix == ".npz":
+        with open(path, "wb") as f:          # (a file object: numpy appends no second suffix)
+            np.savez(f, **arrays)
+    elif suffix == ".json":
+        with open(path, "w") as f:
+            json.dump({k: v.tolist() for k, v in arrays.items()}, f)
+    elif suffix == ".pkl":
+        import pickle
+        with open(path, "wb") as f:
+            pickle.dump(dict(arrays), f)
+    elif suffix == ".csv":
+        import csv
+        with open(path, "w", newline="") as f:
+            wr = csv.writer(f)
+            cols = None
+            for name, arr in arrays.items():
+                if cols is None:
+                    cols = _agent_columns(arr.shape[1])
+                    wr.writerow(["Configuration", "Episode"] + cols)
+                elif len(cols) != arr.shape[1]:
+                    raise ValueError("the configurations of one CSV file must have the same number of agents")
+                for i, row in enumerate(arr):
+                    wr.writerow([name, i] + [repr(float(x)) for x in row])
+            if cols is None:
+                wr.writerow(["Configuration", "Episode"])
+    else:
+        raise ValueError(f"episodes file {path!r}: the suffix must be .npz, .json, .pkl or .csv")
+
+
+def save_combinations(path: str, logs: Dict[str, EpisodeLog]) -> None:
+    """:func:`evaluate_combinations`' logs {desc: EpisodeLog} as the configurations ``Config_<desc>``
+    (Config_BB, Config_BL, Config_LB, Config_LL for two types) of one such file."""
+    _save_reward_arrays(path, {f"Config_{desc}": log.rewards().numpy() for desc, log in logs.items()})
 
 
 MAX_DRAW_ACTIONS = 32   # the actions of a drawn type: one 32-bit mask, one lane per action
@@ -446,13 +671,24 @@ def _key_chain(rng: torch.Tensor, n_steps: int, partitionable: bool):
     return rng, sub, act
 
 
+def _new_episodes(env, n_envs: int, max_episodes: Optional[int]) -> Optional[torch.Tensor]:
+    """the zeroed records buffer of an evaluation with ``max_episodes`` (None: no records)"""
+    if max_episodes is None:
+        return None
+    return torch.zeros((n_envs, len(env.layout.agent_kinds), _check_cap(max_episodes), EPISODE_WORDS),
+                       dtype=torch.float64, device=env.device)
+
+
 def evaluate_fixed_actions(env, fixed_actions: Sequence, n_envs: int, n_steps: int, seed: int,
-                           chunk: int = 256) -> EvalStats:
+                           chunk: int = 256, max_episodes: Optional[int] = None):
     """baseline_only_JAXMARL.py's evaluation: reset ``n_envs`` envs, step them ``n_steps`` times
     with one fixed action per agent type, and reduce.  The keys follow the shape of the script's
     chain from ``PRNGKey(seed)``: ``rng, _rng = split(rng)`` and ``split(_rng, n_envs)`` for the
     reset, then :func:`eval_keys` per step, generated ``chunk`` steps at a time on the device; one
-    ``rollout_eval(fixed=True)`` launch per chunk carries the stats over."""
+    ``rollout_eval(fixed=True)`` launch per chunk carries the stats over.  Returns the
+    :class:`EvalStats`; with ``max_episodes`` the launches also keep each env's first ``max_episodes``
+    episodes' records, in one buffer carried across the chunks, and the return value is
+    ``(EvalStats, EpisodeLog)``."""
     from .env import split_keys
     if n_envs < 1 or n_steps < 1 or chunk < 1:
         raise ValueError("n_envs, n_steps and chunk must be >= 1")
@@ -464,20 +700,26 @@ def evaluate_fixed_actions(env, fixed_actions: Sequence, n_envs: int, n_steps: i
     rng = pair[:, 0].contiguous()
     _, state = env.reset(split_keys(pair[:, 1].contiguous(), n_envs, part)[0], params)
     stats = None
+    episodes = _new_episodes(env, n_envs, max_episodes)
     for t0 in range(0, n_steps, chunk):
         rng, keys = eval_keys(rng, n_envs, min(chunk, n_steps - t0), part)
-        stats = env.rollout_eval(keys, state, row, params, stats=stats, fixed=True)[-1]
-    return EvalStats(stats, env.layout)
+        stats = env.rollout_eval(keys, state, row, params, stats=stats, fixed=True, episodes=episodes)[5]
+    if episodes is None:
+        return EvalStats(stats, env.layout)
+    return EvalStats(stats, env.layout), EpisodeLog(episodes, stats, env.layout)
 
 
-def evaluate_baseline(env, entries: Sequence, n_envs: int, n_steps: int, seed: int, chunk: int = 256) -> EvalStats:
+def evaluate_baseline(env, entries: Sequence, n_envs: int, n_steps: int, seed: int, chunk: int = 256,
+                      max_episodes: Optional[int] = None):
     """:func:`evaluate_fixed_actions` for baselines that draw: ``entries`` holds one int, list of one
     int or :class:`Uniform` per agent type, in any mix, and one ``rollout_eval_drawn`` launch per
     chunk draws every type's actions inside the env launch (a fixed action is a mask of one bit, which
     draws nothing).  The reset and step keys are that function's chain unchanged; type i's draw key at
     a step is ``split(act, n_types)[i]`` of the key the chain leaves unused (:func:`_key_chain`), what
     :func:`evaluate_policy` hands the type, so the two give the same stats for the same entries.  Every
-    type needs a Discrete space of at most 32 actions, and a :class:`Uniform` partitionable keys."""
+    type needs a Discrete space of at most 32 actions, and a :class:`Uniform` partitionable keys.
+    ``max_episodes``: as :func:`evaluate_fixed_actions` takes it (the return value becomes
+    ``(EvalStats, EpisodeLog)``; the records are the same for the same entries too)."""
     from .env import split_keys
     if n_envs < 1 or n_steps < 1 or chunk < 1:
         raise ValueError("n_envs, n_steps and chunk must be >= 1")
@@ -495,12 +737,15 @@ def evaluate_baseline(env, entries: Sequence, n_envs: int, n_steps: int, seed: i
     rng = pair[:, 0].contiguous()
     _, state = env.reset(split_keys(pair[:, 1].contiguous(), n_envs, part)[0], params)
     stats = None
+    episodes = _new_episodes(env, n_envs, max_episodes)
     for t0 in range(0, n_steps, chunk):
         rng, sub, act = _key_chain(rng, min(chunk, n_steps - t0), part)
         keys = split_keys(torch.cat(sub).contiguous(), n_envs, part)                      # [T, E, 2]
         draw_keys = split_keys(torch.cat(act).contiguous(), n_types, part)                # [T, n_types, 2]
-        stats = env.rollout_eval_drawn(keys, state, draw_keys, allowed, params, stats=stats)[-1]
-    return EvalStats(stats, env.layout)
+        stats = env.rollout_eval_drawn(keys, state, draw_keys, allowed, params, stats=stats, episodes=episodes)[5]
+    if episodes is None:
+        return EvalStats(stats, env.layout)
+    return EvalStats(stats, env.layout), EpisodeLog(episodes, stats, env.layout)
 
 
 def _fixed_action(t: int, a) -> int:
@@ -526,7 +771,7 @@ def policy_entries(nets: Sequence, n_types: int) -> list:
 
 
 def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: bool = True,
-                    chunk: int = 64, grouped: bool = False) -> EvalStats:
+                    chunk: int = 64, grouped: bool = False, max_episodes: Optional[int] = None):
     """:func:`evaluate_fixed_actions` with recurrent policies in place of the fixed actions: ``nets``
     holds one entry per agent type, an ``ActorCriticRNN`` (``hftlob.train.ippo.load_policy``) or a
     fixed action (an int, or a list of one int), in any mix.  Every agent of a fixed type, and every
@@ -544,7 +789,9 @@ def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: boo
     carry either, and its step is one :func:`draw_actions` launch under the type's policy key of the
     step, the key a learned type would sample with; learned and fixed types are as without it.
     ``grouped``: the learned types' steps of a step are one launch (``train.policy.policy_step_grouped``: at
-    most 8 learned types of one FC_DIM_SIZE and GRU_HIDDEN_DIM), with the same statistics bit for bit."""
+    most 8 learned types of one FC_DIM_SIZE and GRU_HIDDEN_DIM), with the same statistics bit for bit.
+    ``max_episodes``: every step's tally launch also writes the records of the episodes that end there
+    (hftlob_eval_tally_episodes) into one buffer, and the return value is ``(EvalStats, EpisodeLog)``."""
     from .env import split_keys
     from .train.policy import GREEDY, SAMPLE, policy_step_grouped, policy_step_grouped_supported, policy_step_net
     if n_envs < 1 or n_steps < 1 or chunk < 1:
@@ -578,6 +825,7 @@ def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: boo
     masks = _float_word_masks(L)
     A = len(L.agent_kinds)
     stats = torch.zeros((E, A, EVAL_WORDS), dtype=torch.float64, device=dev)
+    episodes = _new_episodes(env, E, max_episodes)
     for t0 in range(0, n_steps, chunk):
         T = min(chunk, n_steps - t0)
         rng, sub, act = _key_chain(rng, T, part)
@@ -597,11 +845,13 @@ def evaluate_policy(env, nets, n_envs: int, n_steps: int, seed: int, greedy: boo
             o, state, _, d, _ = env.step(keys[t], state, actions, params)
             # the step's raw outputs where the env launch wrote them: [E, A], [E, info_words], [E]
             _tally_launch(env.last_rewards.view(1, E, A), env.last_info_words.view(1, E, L.info_words),
-                          d["__all__"].view(torch.uint8).view(1, E), masks, L.info_words, stats)
+                          d["__all__"].view(torch.uint8).view(1, E), masks, L.info_words, stats, episodes)
             for i in learned:
                 obs[i] = o[i].reshape(n_act[i], -1).contiguous()
                 done[i] = d["agents"][i].reshape(-1).contiguous()
-    return EvalStats(stats, L)
+    if episodes is None:
+        return EvalStats(stats, L)
+    return EvalStats(stats, L), EpisodeLog(episodes, stats, L)
 
 
 def combination_names(n_types: int) -> List[str]:
@@ -622,17 +872,19 @@ def mix_entries(desc: str, nets: Sequence, fixed_actions: Sequence) -> list:
 
 
 def evaluate_combinations(env, nets, fixed_actions: Sequence, n_envs: int, n_steps: int, seed: int,
-                          greedy: bool = True) -> Dict[str, EvalStats]:
+                          greedy: bool = True, max_episodes: Optional[int] = None) -> dict:
     """baseline_JAXMARL.py's evaluation (:819-951): every combination of the learned policy
     (``nets[t]``) and the baseline (``fixed_actions[t]``) per agent type through
     :func:`evaluate_policy`, all under the same seed, so the runs are paired as the reference's are
     (it passes the same rng to each).  Returns {name: EvalStats} in :func:`combination_names`' order.
     One env config serves all combinations (the reference's per-combination agent configs are not
-    covered)."""
+    covered).  With ``max_episodes`` the values are ``(EvalStats, EpisodeLog)``
+    (:func:`save_combinations` writes the logs as the reference's plots read them)."""
     n = len(env.multi_agent_config.number_of_agents_per_type)
     policy_entries(nets, n)
     policy_entries(fixed_actions, n)
-    return {desc: evaluate_policy(env, mix_entries(desc, nets, fixed_actions), n_envs, n_steps, seed, greedy=greedy)
+    return {desc: evaluate_policy(env, mix_entries(desc, nets, fixed_actions), n_envs, n_steps, seed, greedy=greedy,
+                                  max_episodes=max_episodes)
             for desc in combination_names(n)}
 
 
@@ -684,6 +936,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help="steps per launch (default 256), or with --checkpoint per key generation (default 64)")
     ap.add_argument("--data-msgs", type=int, default=400_000, help="length of the synthetic message day")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--episodes-out", metavar="PATH",
+                    help="write the episode rewards [episodes, agents] to PATH as the reference's "
+                         "plotting_combinations.py loads them (.npz, .json, .pkl or .csv by the suffix); the JSON "
+                         "object gains the records' digest")
+    ap.add_argument("--max-episodes", type=int, default=128,
+                    help="with --episodes-out: the records kept per env (default 128); later episodes are counted as "
+                         "dropped")
     return ap
 
 
@@ -702,6 +961,26 @@ def main(argv=None) -> int:
     from .data.synthetic import generate_day
     from .env import MARLEnv
     cfg = load_config_from_file(args.env_config) if os.path.exists(args.env_config) else builtin_config(args.env_config)
+    cap = None
+    if args.episodes_out:
+        if os.path.splitext(args.episodes_out)[1].lower() not in (".npz", ".json", ".pkl", ".csv"):
+            ap.error("--episodes-out: the suffix must be .npz, .json, .pkl or .csv")
+        if args.max_episodes < 1:
+            ap.error("--max-episodes must be >= 1")
+        cap = args.max_episodes
+
+    def finish(out: dict, ev) -> int:
+        """one evaluation's JSON line; with --episodes-out also its records file and digest"""
+        if cap is not None:
+            ev, log = ev
+        out.update(ev.summary())
+        if cap is not None:
+            log.save(args.episodes_out)
+            out["episodes"] = log.summary()
+            out["episodes_dropped"] = log.dropped
+        print(json.dumps(out))
+        return 0
+
     w = cfg.world_config
     day = generate_day(n_msgs=args.data_msgs, snap_every=w.n_data_msg_per_step * w.start_resolution)
     if args.checkpoint:
@@ -714,36 +993,39 @@ def main(argv=None) -> int:
                    "baseline_actions": [entry_spelling(p) for p in base], "envs": args.envs, "steps": args.steps,
                    "seed": args.seed}
             if args.combinations:
-                evs = evaluate_combinations(env, nets, base, args.envs, args.steps, args.seed, greedy=not args.sample)
+                evs = evaluate_combinations(env, nets, base, args.envs, args.steps, args.seed, greedy=not args.sample,
+                                            max_episodes=cap)
             else:
                 evs = {args.mix: evaluate_policy(env, mix_entries(args.mix, nets, base), args.envs, args.steps,
-                                                 args.seed, greedy=not args.sample, chunk=args.chunk or 64)}
+                                                 args.seed, greedy=not args.sample, chunk=args.chunk or 64,
+                                                 max_episodes=cap)}
+            if cap is not None:
+                logs = {desc: log for desc, (_, log) in evs.items()}
+                evs = {desc: ev for desc, (ev, _) in evs.items()}
             out["combinations"] = {desc: ev.summary() for desc, ev in evs.items()}
+            if cap is not None:
+                save_combinations(args.episodes_out, logs)
+                out["episodes"] = {desc: log.summary() for desc, log in logs.items()}
+                out["episodes_dropped"] = sum(log.dropped for log in logs.values())
             print(json.dumps(out))
             return 0
         ev = evaluate_policy(env, nets, args.envs, args.steps, args.seed, greedy=not args.sample,
-                             chunk=args.chunk or 64)
+                             chunk=args.chunk or 64, max_episodes=cap)
         out = {"env_config": args.env_config, "checkpoint": args.checkpoint, "sample": bool(args.sample),
                "envs": args.envs, "steps": args.steps, "seed": args.seed}
-        out.update(ev.summary())
-        print(json.dumps(out))
-        return 0
+        return finish(out, ev)
     env = MARLEnv(None, cfg, data=day, device=args.device, return_info=False, persistent_outputs=True)
     if args.uniform_actions:
         entries = parse_entries(args.uniform_actions)
-        ev = evaluate_baseline(env, entries, args.envs, args.steps, args.seed, args.chunk or 256)
+        ev = evaluate_baseline(env, entries, args.envs, args.steps, args.seed, args.chunk or 256, max_episodes=cap)
         out = {"env_config": args.env_config, "uniform_actions": [entry_spelling(p) for p in entries],
                "envs": args.envs, "steps": args.steps, "seed": args.seed}
-        out.update(ev.summary())
-        print(json.dumps(out))
-        return 0
+        return finish(out, ev)
     actions = [int(x) for x in args.fixed_actions.split(",")]
-    ev = evaluate_fixed_actions(env, actions, args.envs, args.steps, args.seed, args.chunk or 256)
+    ev = evaluate_fixed_actions(env, actions, args.envs, args.steps, args.seed, args.chunk or 256, max_episodes=cap)
     out = {"env_config": args.env_config, "fixed_actions": actions, "envs": args.envs, "steps": args.steps,
            "seed": args.seed}
-    out.update(ev.summary())
-    print(json.dumps(out))
-    return 0
+    return finish(out, ev)
 
 
 if __name__ == "__main__":
