@@ -49,6 +49,8 @@
  *                           MultiCategorical: one categorical head per word of a MultiDiscrete space.
  *   hftlob_policy_step_grouped <- the same steps of several independent nets (IPPO's one net per agent
  *                           type; the runs of a sweep, :1274 wandb.agent) as one launch.
+ *   hftlob_rollout_diag / hftlob_world_tally <- jaxrl/MARL/ippo_rnn_JAXMARL.py:977-1059, the update callback's
+ *                           reductions of the trajectory batch (action shares, info means and stds).
  */
 #ifndef HFTLOB_H
 #define HFTLOB_H
@@ -960,6 +962,68 @@ int hftlob_xty_wide(long long N, int Q, const float* A0, int cols0, long long st
                     long long stride1, const float* B /*[N][Q]*/, const float* head /*[shift][Q] or NULL*/,
                     long long shift, const unsigned char* zero_row /*[N] or NULL*/, float* C /*[P][Q]*/,
                     float* sum_a /*[P] or NULL*/, float* workspace, void* stream);
+
+/* The training diagnostics: one agent type's rollout buffers reduced to HFTLOB_DIAG_WORDS doubles.  N = T *
+ * n_actors elements, every array contiguous: action int32 [N][K] (K heads, head k of nvec[k] actions; the
+ * limits are hftlob_ppo_loss's, 1 <= K <= HFTLOB_DIAG_MAX_HEADS and 1 <= nvec[k] <= HFTLOB_DIAG_MAX_ACTIONS),
+ * reward, value, log_prob, adv, target float32 [N], done bytes [N] (the env's global done).  Words of diag:
+ *    0          N
+ *    1          the number of set (nonzero) done bytes
+ *    2 + 2q     the sum of quantity q over the N elements, q = 0 reward, 1 value, 2 log_prob, 3 advantage,
+ *    3 + 2q     4 target, 5 residual = (double)target - (double)value; and the sum of its squares
+ *   14 + k      the sum of head k's action words that lie in [0, nvec[k])
+ *   18 + k      the count of head k's action words outside [0, nvec[k]) (in no bin, not in the sum)
+ *   22 + 16k + a   the count of head k's action a
+ * Every value is widened to double before it is subtracted, squared or added; a square is one rounded double
+ * product, added separately (no fused multiply-add).  Words of heads k >= K and of actions a >= nvec[k] are 0.
+ * Two launches on the caller's stream:
+ *   the partial pass cuts the elements into G contiguous stripes, one per workgroup of 256 lanes.  The stripe
+ *     rule is a function of N alone, with R = HFTLOB_DIAG_STRIPE_ROWS, M = HFTLOB_DIAG_MAX_STRIPES:
+ *         rows = R if ceil(N / R) <= M, else ceil(N / M)        G = ceil(N / rows)
+ *     stripe g is the elements [g rows, min(N, (g + 1) rows)): up to M stripes of R elements, and past M R
+ *     elements the stripes grow instead of their number; none is empty.  Lane l starts every one of the
+ *     twelve words 2..13 at +0.0 and adds the stripe's elements begin + l, begin + l + 256, ... in that
+ *     order; the stripe's partial of a word is the 256 lanes' sums added in lane order, from lane 0's (a
+ *     lane without an element contributes its +0.0).  The counts are integers, exact in any order.  The
+ *     workgroup leaves its partial of HFTLOB_DIAG_WORDS doubles in the workspace;
+ *   the final pass adds the G partials of every word in stripe order, from stripe 0's.
+ * No floating-point atomic and a fixed order of every sum: the same inputs give the same bits on every call,
+ * eager or replayed from a HIP graph.  Elements past N are never read.  workspace is the caller's,
+ * hftlob_rollout_diag_workspace(N) doubles (G HFTLOB_DIAG_WORDS; a host-only function that makes no device
+ * call), written before it is read.  N = 0 zero-fills diag with an asynchronous memset and reads nothing: the
+ * arrays and workspace may then be NULL.  The call neither allocates nor synchronises and can be captured in
+ * a HIP graph.  Checked in this order, before any device work: HFTLOB_ESHAPE: N < 0
+ * (hftlob_rollout_diag_workspace returns the same code, as a negative size), K outside
+ * 1..HFTLOB_DIAG_MAX_HEADS; HFTLOB_ENULL: a NULL nvec or diag, or with N > 0 a NULL array or workspace;
+ * HFTLOB_EINVAL: an nvec entry outside 1..HFTLOB_DIAG_MAX_ACTIONS.  hftlob/train/diag.py restates it in torch
+ * (rollout_diag_reference). */
+#define HFTLOB_DIAG_MAX_HEADS 4
+#define HFTLOB_DIAG_MAX_ACTIONS 16
+#define HFTLOB_DIAG_WORDS 86
+#define HFTLOB_DIAG_STRIPE_ROWS 1024   /* R: the elements of a stripe up to HFTLOB_DIAG_MAX_STRIPES stripes */
+#define HFTLOB_DIAG_MAX_STRIPES 256    /* M: the most stripes (workgroups of the partial pass) */
+long long hftlob_rollout_diag_workspace(long long N);   /* doubles; < 0: an error code; host only */
+int hftlob_rollout_diag(long long N, int K, const int* nvec /*[K], host*/,
+                        const int32_t* action /*[N][K]*/, const float* reward, const float* value,
+                        const float* log_prob, const float* adv, const float* target /*[N] each*/,
+                        const uint8_t* done /*[N]*/, double* diag /*[HFTLOB_DIAG_WORDS], written*/,
+                        double* workspace, void* stream);
+
+/* The world half of hftlob_eval_tally: the world info words (the first HFTLOB_INFO_WORLD_WORDS words of an
+ * env's info record) of n_steps steps folded into per-env sums.  info int32 [n_steps][n_env][info_words] as
+ * the step launches write hftlob_step_out.info; float_words: bit k set = world word k is a float32 (it is
+ * widened from the float with the word's bits, else from the int32).  wstats double
+ * [n_env][HFTLOB_WORLD_TALLY_WORDS], in/out: word 2k receives the sum of world word k over the steps, in
+ * step order, word 2k + 1 the sum of its squares (one rounded double product each, added separately), both
+ * ADDED to what the call finds.  One lane per (env, word), sequential over the steps: bit for bit a float64
+ * loop (hftlob/train/diag.py world_tally_reference).  One launch on the caller's stream; the call neither
+ * allocates nor synchronises and can be captured in a HIP graph.  Checked in this order, before any device
+ * work: HFTLOB_ESHAPE: n_env < 1, n_steps < 1, info_words < HFTLOB_INFO_WORLD_WORDS; HFTLOB_ENULL: a NULL
+ * info or wstats; HFTLOB_EINVAL: a bit of float_words at or above HFTLOB_INFO_WORLD_WORDS. */
+#define HFTLOB_WORLD_TALLY_WORDS 28   /* 2 * 14 world info words */
+int hftlob_world_tally(int n_env, int n_steps, int info_words, const int32_t* info /*[n_steps][n_env][info_words]*/,
+                       uint32_t float_words /*bit k: world word k is a float*/,
+                       double* wstats /*[n_env][HFTLOB_WORLD_TALLY_WORDS], in/out*/, void* stream);
 
 #ifdef __cplusplus
 }

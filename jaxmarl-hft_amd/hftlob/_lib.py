@@ -52,6 +52,10 @@ LIB_PATH = os.environ.get("HFTLOB_LIB") or os.path.join(os.path.dirname(os.path.
 ABI_VERSION = 8
 EVAL_WORDS = 106  # HFTLOB_EVAL_WORDS: doubles per agent in hftlob_env_rollout_eval's stats (the table is in hftlob.h)
 EPISODE_WORDS = 26  # HFTLOB_EPISODE_WORDS: doubles per (env, agent, completed episode) in the episodes buffers
+DIAG_WORDS = 86  # HFTLOB_DIAG_WORDS: doubles of hftlob_rollout_diag's result (the table is in hftlob.h)
+DIAG_MAX_HEADS, DIAG_MAX_ACTIONS = 4, 16  # HFTLOB_DIAG_MAX_HEADS, HFTLOB_DIAG_MAX_ACTIONS
+DIAG_STRIPE_ROWS, DIAG_MAX_STRIPES = 1024, 256  # HFTLOB_DIAG_STRIPE_ROWS, HFTLOB_DIAG_MAX_STRIPES: the stripe rule
+WORLD_TALLY_WORDS = 28  # HFTLOB_WORLD_TALLY_WORDS: doubles per env in hftlob_world_tally's wstats
 EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob_book_depth",
            "hftlob_book_process_depth", "hftlob_env_reset",
            "hftlob_env_step", "hftlob_env_step_sampled", "hftlob_env_rollout_sampled", "hftlob_rollout_prepare",
@@ -62,7 +66,8 @@ EXPORTS = ("hftlob_version", "hftlob_last_error", "hftlob_book_process", "hftlob
            "hftlob_sample_actions", "hftlob_split_keys", "hftlob_gru_scan_fwd", "hftlob_gru_scan_bwd",
            "hftlob_gru_scan_fwd_grouped", "hftlob_gru_scan_bwd_grouped",
            "hftlob_policy_step", "hftlob_policy_step_multi", "hftlob_policy_step_grouped", "hftlob_gae", "hftlob_ppo_loss",
-           "hftlob_adam_clip", "hftlob_xty", "hftlob_xty_workspace", "hftlob_xty_wide", "hftlob_xty_wide_workspace")
+           "hftlob_adam_clip", "hftlob_xty", "hftlob_xty_workspace", "hftlob_xty_wide", "hftlob_xty_wide_workspace",
+           "hftlob_rollout_diag", "hftlob_rollout_diag_workspace", "hftlob_world_tally")
 
 _lib = None
 
@@ -163,6 +168,12 @@ def lib() -> C.CDLL:
     L.hftlob_xty_wide.restype = i32
     L.hftlob_xty_wide_workspace.argtypes = [C.c_longlong, i32, i32]
     L.hftlob_xty_wide_workspace.restype = C.c_longlong
+    L.hftlob_rollout_diag.argtypes = [C.c_longlong, i32, C.POINTER(i32), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.hftlob_rollout_diag.restype = i32
+    L.hftlob_rollout_diag_workspace.argtypes = [C.c_longlong]
+    L.hftlob_rollout_diag_workspace.restype = C.c_longlong
+    L.hftlob_world_tally.argtypes = [i32, i32, i32, vp, C.c_uint32, vp, vp]
+    L.hftlob_world_tally.restype = i32
     if L.hftlob_version() != ABI_VERSION:
         raise RuntimeError(f"libhftlob ABI {L.hftlob_version()} != {ABI_VERSION}")
     _lib = L

@@ -157,7 +157,14 @@ class MARLEnv:
         """data: a synthetic ``LobsterDay`` (None = the seeded default day), a ``LoadedDay`` from
         ``hftlob.data.lobster``, or ``"lobster"`` to load ``world_config.dataPath`` /
         ``stock`` / ``timePeriod`` through ``LoadLOBSTER_resample`` as the reference's
-        ``BaseLOBEnv.__init__`` does (base_env.py:157-176)."""
+        ``BaseLOBEnv.__init__`` does (base_env.py:157-176).
+        return_info: True builds the info dict of every step; False writes no info record at all;
+        ``"raw"`` has the launches write the info record as True does (``last_info_words`` and
+        ``last_rewards`` are set the same) but builds no dict: ``step``, ``step_sampled`` and the rollouts
+        return ``{}``, and no ``obs_raw`` or ``debug`` output is allocated (the training diagnostics'
+        mode: the dict costs one ``index_select`` per agent info field and agent type at every step)."""
+        if isinstance(return_info, str) and return_info != "raw":
+            raise ValueError(f"return_info must be True, False or 'raw', got {return_info!r}")
         self.multi_agent_config = cfg = multi_agent_config
         self.device = torch.device(device or "cuda")
         w = cfg.world_config
@@ -201,7 +208,7 @@ class MARLEnv:
         # world debug_mode (marl_env.py:645-656): info["world"] also carries the step's trades, its
         # combined messages and the 10-level lob_state of the stepped books
         self.debug_mode = bool(w.debug_mode)
-        self.return_info = return_info
+        self.return_info = "raw" if return_info == "raw" else bool(return_info)
         self.persistent_outputs = persistent_outputs
         self._out = None
         self._init_states = self._precompute_init_states()
@@ -268,8 +275,8 @@ class MARLEnv:
     def _alloc(self, lead: tuple):
         """Output buffers of `lead` (E,) or (T, E) env steps and their hftlob_step_out."""
         L, dev, A = self.layout, self.device, self.num_agents
-        want_raw = self.save_raw_observations and self.return_info
-        want_dbg = self.debug_mode and self.return_info
+        want_raw = self.save_raw_observations and self.return_info is True
+        want_dbg = self.debug_mode and self.return_info is True
         o = {"obs": torch.empty(lead + (A, L.obs_stride), dtype=torch.float32, device=dev),
              "rewards": torch.empty(lead + (A,), dtype=torch.float32, device=dev),
              "done_all": torch.empty(lead, dtype=torch.bool, device=dev),
@@ -330,7 +337,7 @@ class MARLEnv:
         return cache[key]
 
     def _info(self, o, E):
-        if o["info"] is None:
+        if o["info"] is None or self.return_info == "raw":   # "raw": the record alone (last_info_words), no dict
             return {}
         info = o["info"]
         f = info.view(torch.float32)

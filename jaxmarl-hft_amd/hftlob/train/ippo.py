@@ -53,6 +53,13 @@ with rocBLAS, and parameters, ``state_dict`` and checkpoints are untouched.
 ``critic1``: ``train.wgrad.wide_linear``, the product on the matrix cores), and with ``FUSED_GRU`` for the
 GRU's ``weight_hh`` (``train.gru.weight_grads_fused``, which also drops the concatenations and the select that
 built its operands).
+With ``TRAIN_DIAG`` (an env built with ``return_info="raw"``) every rollout step's rewards, info record and global
+done are folded into per-agent and per-env accumulators on the device (``train.diag.RolloutTally``: the evaluation
+tally and a world tally, inside the captured rollout), after GAE each agent type's buffers are reduced to a few
+words (``train.diag.rollout_diag``), and ``metrics["diag"]`` is the update's ``train.diag.TrainDiag``: the action
+shares, info means and stds, episode counts and explained variance the reference's update callback (:977-1059)
+logs.  It reads what the update wrote and writes only tensors of its own, so training is bit for bit what it is
+without it.
 """
 from __future__ import annotations
 
@@ -69,6 +76,8 @@ from ..env import MARLEnv, split_keys
 from .gru import MAX_GROUPS, SUPPORTED_HIDDEN, gru_scan, gru_scan_grouped, gru_scan_supported
 from .loss import gae as gae_fused, ppo_loss_fused, ppo_loss_supported
 from .optim import MAX_TENSORS, adam_clip_step, adam_clip_supported, init_adam_state
+from .diag import (DIAG_MAX_ACTIONS, DIAG_MAX_HEADS, DIAG_WORDS, RolloutTally, TrainDiag, diag_supported, diag_workspace,
+                   rollout_diag, rollout_diag_reference)
 from .policy import (MAX_ACTIONS, MAX_GROUPS as MAX_POLICY_GROUPS, MAX_HEADS, MAX_OBS_DIM, SAMPLE, policy_step_grouped,
                      policy_step_multi_supported, policy_step_net)
 from .wgrad import MAX_P, SUPPORTED_Q, narrow_linear, narrow_linear_supported, wide_linear, wide_linear_supported
@@ -132,9 +141,15 @@ def _wgrad_wide_check(n, c):
                 f"{c['GRU_HIDDEN_DIM']} and {c['FC_DIM_SIZE']}")
 
 
+def _diag_check(n, c):
+    if not diag_supported(n.heads):
+        return (f"TRAIN_DIAG needs <= {DIAG_MAX_ACTIONS} actions (in each of <= {DIAG_MAX_HEADS} heads), got "
+                f"{n.heads}")
+
+
 # Every switch, in the order the trainer checks them.  The module docstring says what each one does; what a
 # switch needs beyond a device and a per-net check (FUSED_GRU's hidden size and its CPU rule, GROUPED_SCAN's
-# three conditions, CALC_EVAL's eval env) is in IPPOTrainer.__init__.
+# three conditions, CALC_EVAL's eval env, TRAIN_DIAG's env mode) is in IPPOTrainer.__init__.
 SWITCHES = [
     Switch("FUSED_GRU", "the PPO update's GRU scan as the fused HIP operators", gpu=False),   # on the CPU: the loop
     Switch("FUSED_POLICY", "the rollout's policy step, sample and log-prob as one fused HIP launch",
@@ -153,6 +168,9 @@ SWITCHES = [
     Switch("CALC_EVAL", "CALC_EVAL: after every update NUM_STEPS_EVAL sampled steps in a separate eval env (the same "
            "config, a synthetic day of another seed), logged as avg_reward_eval",
            check=_policy_step_check("CALC_EVAL runs the fused policy step: it needs")),
+    Switch("TRAIN_DIAG", "per-update diagnostics tallied on the device (action shares, info means and stds, episodes, "
+           "explained variance), logged as diag; the env is built with return_info='raw'", gpu=False,
+           check=_diag_check),   # on the CPU: train.diag's reference functions
 ]
 
 
@@ -365,14 +383,19 @@ def _average_grads(params, dist) -> None:
         o += g.numel()
 
 
-def rollout_members(members: Sequence["IPPOTrainer"], env, state):
+def rollout_members(members: Sequence["IPPOTrainer"], env, state, tally: Optional[RolloutTally] = None):
     """NUM_STEPS of _env_step (:578-658) for the trainers ``members`` (one, or the several of a
     ``PopulationTrainer``) on one env batch whose rows [m E, (m + 1) E) are member m's; returns the env state.
     Per step: every member's policy side (with GROUPED_POLICY all the members' and types' steps as ONE launch),
     ONE ``env.step`` whose keys and per-type actions are the members' own concatenated, then every member's
-    rows of the outputs into its buffers.  One member concatenates and slices nothing."""
+    rows of the outputs into its buffers.  One member concatenates and slices nothing.
+    With ``tally`` (TRAIN_DIAG: the accumulators of the whole env batch) the words of the update before are
+    cleared at the top but for the running episode's, and every step's rewards, info record and global dones
+    are folded in after its ``env.step``: one agents' tally and one world tally per step, on the same stream."""
     lead, P = members[0], len(members)
     E = lead.E
+    if tally is not None:
+        tally.begin()
     for t in range(lead.T):
         jobs: list = []
         actions = [m._policy_step(t, jobs) for m in members]
@@ -385,6 +408,8 @@ def rollout_members(members: Sequence["IPPOTrainer"], env, state):
         else:
             keys, acts = torch.cat(keys), [torch.cat(a) for a in zip(*actions)]
         obs, state, rew, dones, _ = env.step(keys, state, acts, lead.params)
+        if tally is not None:
+            tally.step(env, dones)
         for k, m in enumerate(members):
             if P == 1:
                 m._env_outputs(t, obs, rew, dones)
@@ -541,6 +566,9 @@ class IPPOTrainer:
                 raise ValueError(f"NUM_STEPS_EVAL must be >= 1, got {self.T_eval}")
             if eval_env is None or not getattr(eval_env, "return_info", False):
                 raise ValueError("CALC_EVAL needs eval_env, a second MARLEnv built with return_info=True")
+        # TRAIN_DIAG: the rollout's steps tallied from the env's raw info record (train.diag)
+        if c.get("TRAIN_DIAG", False) and not getattr(env, "return_info", False):
+            raise ValueError('TRAIN_DIAG needs an env that writes the info record: build it with return_info="raw"')
         # every switch as the attribute of its name in lower case (fused_policy, fused_loss, fused_opt, grouped_scan,
         # fused_wgrad, fused_wgrad_wide, calc_eval, ...); one that is on passes its device and per-net checks
         for sw in SWITCHES:
@@ -613,6 +641,16 @@ class IPPOTrainer:
                      "tgt": torch.empty((T, n), device=self.device),
                      "idx": torch.zeros(n // c["NUM_MINIBATCHES"], dtype=torch.long, device=self.device)}
                     for n in self.n_actors]
+        # TRAIN_DIAG: the rollout's accumulators (a population's members share its tally: _diag_rows is then a
+        # member's rows of it), each type's rollout_diag words and workspace, and the first minibatch step's scalars
+        self._tally = RolloutTally(env, self.E, self.device) if self.train_diag and reset else None
+        self._diag_rows = slice(0, self.E)
+        if self.train_diag:
+            self._diag_words = [torch.zeros(DIAG_WORDS, dtype=torch.float64, device=self.device)
+                                for _ in self.n_actors]
+            self._diag_ws = [torch.empty(max(1, diag_workspace(T * n)), dtype=torch.float64, device=self.device)
+                             for n in self.n_actors]
+        self._first = [None] * nt
 
     def _adopt_obs(self, obs) -> None:
         """The first observations after the reset, per agent type [E, n, D]."""
@@ -640,7 +678,7 @@ class IPPOTrainer:
         return r
 
     def _rollout(self) -> None:
-        self.state = rollout_members([self], self.env, self.state)
+        self.state = rollout_members([self], self.env, self.state, self._tally)
 
     def _policy_step(self, t: int, jobs: list) -> list:
         """The policy side of rollout step t: per agent type the obs and done rows into the buffers, then the
@@ -704,6 +742,11 @@ class IPPOTrainer:
             gae_fn = gae_fused if self.fused_loss else calculate_gae
             adv, targets = gae_fn(b.reward, b.value, b.global_done, last_val, c["GAMMA"][i], c["GAE_LAMBDA"][i])
             st["h0"].copy_(h0); st["adv"].copy_(adv); st["tgt"].copy_(targets)
+            if self.train_diag:   # the type's rollout reduced to its diag words (eager, outside the graphs)
+                if self.device.type == "cuda":
+                    rollout_diag(b, st["adv"], st["tgt"], net.heads, out=self._diag_words[i], workspace=self._diag_ws[i])
+                else:
+                    self._diag_words[i].copy_(rollout_diag_reference(b, st["adv"], st["tgt"], net.heads))
 
     def _set_lr(self, i: int) -> None:
         """Agent type i's annealed learning rate for its next optimiser step, from its own ``opt_count``."""
@@ -734,6 +777,8 @@ class IPPOTrainer:
                         self._set_lr(i)
                         self._st[i]["idx"].copy_(perms[i][e][m])
                     for i, r in zip(s["types"], self._run_step(s)):
+                        if e == 0 and m == 0:
+                            self._first[i] = r
                         stats[i] += r
                         self.opt_count[i] += 1
         return self._metrics(stats)
@@ -755,6 +800,13 @@ class IPPOTrainer:
             metrics["loss"].append(dict(zip(("total_loss", "value_loss", "actor_loss", "entropy", "approx_kl",
                                              "clip_frac"), stats[i])))
             metrics["avg_reward"].append(b.reward.mean())
+            if self.train_diag:   # the update's first minibatch step (epoch 0, minibatch 0): the reference's ratio_0 check
+                metrics["loss"][i]["approx_kl_0"], metrics["loss"][i]["clip_frac_0"] = self._first[i][4], self._first[i][5]
+        if self.train_diag:
+            tally, rows = self._tally, self._diag_rows
+            metrics["diag"] = TrainDiag(tally.stats[rows], tally.wstats[rows], self._diag_words, self.env.layout,
+                                        [n.heads for n in self.nets], [n.nvec is not None for n in self.nets],
+                                        self.env.type_names)
         if self.calc_eval:
             ev = self.evaluate(self.updates_done)
             metrics["eval"] = ev
@@ -862,6 +914,8 @@ def train(env: MARLEnv, config: Dict, n_updates: Optional[int] = None, dist=None
                    "loss": [{k: float(v) for k, v in d.items()} for d in m["loss"]]}
             if "avg_reward_eval" in m:
                 rec["avg_reward_eval"] = [float(r) for r in m["avg_reward_eval"]]
+            if "diag" in m:
+                rec["diag"] = m["diag"].summary()
             log(rec)
     sync()
     world = dist.get_world_size() if dist is not None else 1
@@ -870,7 +924,7 @@ def train(env: MARLEnv, config: Dict, n_updates: Optional[int] = None, dist=None
 
 def main(argv=None) -> None:
     """python -m hftlob.train.ippo [--rl-config ippo.yaml] [--env-config 2_player_fq_fqc] [--updates N]
-    [switch flags: one per row of SWITCHES, --fused-gru ... --calc-eval]
+    [switch flags: one per row of SWITCHES, --fused-gru ... --calc-eval, --train-diag]
     [--seeds 2,3,4,5 [--overrides sweep.yaml]]: the runs of a sweep as one population (train.population)"""
     import argparse
     import json
@@ -901,7 +955,8 @@ def main(argv=None) -> None:
             c[sw.key] = True
     cfg = (load_config_from_file(a.env_config) if a.env_config.endswith((".json", ".yaml"))
            else builtin_config(a.env_config))
-    env = MARLEnv(None, cfg, data=a.data, return_info=False, persistent_outputs=True)
+    # TRAIN_DIAG reads the steps' raw info record; the info dict is never built
+    env = MARLEnv(None, cfg, data=a.data, return_info="raw" if c["TRAIN_DIAG"] else False, persistent_outputs=True)
     if not a.env_config.endswith((".json", ".yaml")):
         env.config_name = a.env_config   # what a checkpoint records instead of the config's dict
     if a.overrides and not a.seeds:

@@ -10,7 +10,9 @@ members share what is launched, not what is computed:
   step, its keys and actions the members' own, concatenated;
 * with ``GROUPED_POLICY`` one policy-step launch per rollout step for all P x n_types nets;
 * one joint minibatch step over all (member, agent type) pairs: with ``FUSED_GRU`` one scan launch per
-  direction, each pair's loss, clip and Adam with its member's coefficients.
+  direction, each pair's loss, clip and Adam with its member's coefficients;
+* with ``TRAIN_DIAG`` one agents' tally and one world tally per rollout step for the whole batch
+  (``train.diag.RolloutTally``), each member's ``metrics["diag"]`` reading its own rows.
 
 Envs, nets and optimisers are independent, so every member's parameters, optimiser states, buffers, generator
 and metrics are bit for bit those of a solo ``IPPOTrainer(env, config_m)`` with the same switches, and a
@@ -86,11 +88,18 @@ class PopulationTrainer:
         self._joint = {"types": list(range(nt)), "warm": 0, "graph": None, "out": None}
         for m in self.members:
             m._steps = [self._joint]
+        # TRAIN_DIAG: one tally of the whole env batch; member m's diag reads its rows [m E, (m + 1) E)
+        self._tally = None
+        if lead.train_diag:
+            from .diag import RolloutTally
+            self._tally = RolloutTally(env, len(self.members) * self.E, self.device)
+            for k, m in enumerate(self.members):
+                m._tally, m._diag_rows = self._tally, slice(k * self.E, (k + 1) * self.E)
 
     _on_side_stream = IPPOTrainer._on_side_stream
 
     def _rollout(self) -> None:
-        self.state = rollout_members(self.members, self.env, self.state)
+        self.state = rollout_members(self.members, self.env, self.state, self._tally)
 
     @torch.no_grad()
     def rollout(self) -> None:
@@ -118,6 +127,8 @@ class PopulationTrainer:
                 rs = run_joint_step(self._joint, self.pairs, lambda: joint_step(self.pairs), self.graphs,
                                     self._on_side_stream)
                 for (m, i), r in zip(self.pairs, rs):
+                    if e == 0 and k == 0:
+                        m._first[i] = r
                     stats[id(m), i] += r
                     m.opt_count[i] += 1
         return [m._metrics([stats[id(m), i] for i in range(m.n_types)]) for m in members]
@@ -176,9 +187,12 @@ def train_population(env, configs: Sequence[Dict], n_updates: Optional[int] = No
     for u in range(n):
         for k, m in enumerate(pop.update()):
             if log is not None:
-                log({"member": k, "seed": pop.members[k].c["SEED"], "update": u,
-                     "avg_reward": [float(r) for r in m["avg_reward"]],
-                     "loss": [{name: float(v) for name, v in d.items()} for d in m["loss"]]})
+                rec = {"member": k, "seed": pop.members[k].c["SEED"], "update": u,
+                       "avg_reward": [float(r) for r in m["avg_reward"]],
+                       "loss": [{name: float(v) for name, v in d.items()} for d in m["loss"]]}
+                if "diag" in m:
+                    rec["diag"] = m["diag"].summary()
+                log(rec)
     sync()
     return pop, n * pop.T * pop.E * len(pop.members) / (time.perf_counter() - t0)
 
